@@ -10,13 +10,21 @@ kernels = 3 element-updates per cell.  Inputs are resident in HBM before the tim
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU;
                                                         the same 1M-triangle mesh is strip-partitioned: strong scaling)
+  python bench.py --gpus 1 ... --full                  (also the spread of five timed regions, per-launch events, the
+                                                        4M-triangle run and the CPU baseline with its parity check)
+  python bench.py --gpus 1 ... --dump-outputs DIR      (the state after the last timed step, a fixed sample of its cells,
+                                                        as DIR/*.npy in float64)
+
+A plain single-GPU run (no --full) sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+roofline figures of the timed region; everything that takes runs of its own is behind --full.
 
 Clock pre-warm: an MI355X needs ~0.2-0.3 s of sustained load to settle its clocks (measured: 0.147 ms/step right after start
 with W = 10, 0.128 ms/step after 0.3 s of the same work), and W warm-up steps of 0.14 ms are over long before that.  Since
 production runs are thousands of steps, the bench first runs PREWARM_S seconds of the same time stepping (i.e. extra
-untimed warm-up steps; the state simply keeps evolving - a host-side state reset would idle the GPU for ~20 ms and cool it
-down again) and only then does the W untimed warm-up steps and the K timed steps; `config.prewarm_s` reports it
-(--prewarm 0 switches it off).
+untimed warm-up steps; a host-side state reset would idle the GPU for ~20 ms and cool it down again, so the initial state is
+kept in a device-side snapshot and copied back on the device) and only then does the W untimed warm-up steps and the K timed
+steps; `config.prewarm_s` reports it (--prewarm 0 switches it off).  The timed steps therefore always start from the initial
+state advanced by W steps, whatever the pre-warm did: with the same arguments every run computes the same outputs.
 """
 import argparse
 import json
@@ -186,6 +194,22 @@ def beyond_cache(args):
                              'element_updates_per_s': n*3.0*steps/(ms_events*1e-3)}}
 
 
+DUMP_CELLS = 1 << 18                    # --dump-outputs: cells of the fixed sample (21 MB of float64 in all)
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, uv, eta):
+    """What a caller of the timed path receives after its last step - uv (N,3,2) and eta (N,3) in float64 - for a fixed, seeded
+    sample of the cells (the whole state is 72 MB): DIR/uv.npy, DIR/eta.npy and DIR/cells.npy (the sampled cell indices, as
+    float64 to keep every file a floating-point array)."""
+    n = eta.shape[0]
+    cells = np.arange(n) if n <= DUMP_CELLS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_CELLS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'uv.npy'), np.ascontiguousarray(uv[cells], dtype=np.float64))
+    np.save(os.path.join(out_dir, 'eta.npy'), np.ascontiguousarray(eta[cells], dtype=np.float64))
+    np.save(os.path.join(out_dir, 'cells.npy'), cells.astype(np.float64))
+
+
 def run_single(args):
     from thetis_amd.device import Swe2dDevice
     mesh, bath, uv, eta = build_case()
@@ -193,10 +217,12 @@ def run_single(args):
     dev = Swe2dDevice(mesh, bath, DT, device_id=0)
     dev.set_state(uv, eta)
     if args.prewarm > 0:
+        dev.snapshot()
         t0 = time.perf_counter()
         while time.perf_counter() - t0 < args.prewarm:
             dev.advance(200)
             dev.synchronize()
+        dev.restore()                   # a device-side copy: the warm-up and timed steps start from the initial state
     dev.advance(args.warmup)
     dev.synchronize()
     import torch
@@ -209,16 +235,20 @@ def run_single(args):
     t_wall = time.perf_counter() - t0
     # mean stage-kernel launch duration over the timed region: 3 back-to-back launches per step, no gaps in between
     ms_kernel = ms_events/(3.0*args.steps)
-    # the spread of the figure: the same K-step region four more times (the state keeps evolving, no host reset in between);
-    # `value`, `ms_per_step` and `roofline.frac` stay those of the FIRST region (the contract's timed K steps), the samples say
-    # how far one 2-3 ms region is from the next on this box (clock state, Infinity Cache contents)
-    ms_samples = [ms_events] + [dev.advance_timed(args.steps, per_launch=False)[0] for _ in range(4)]
-    frac_samples = [BYTES_PER_ELEMENT_UPDATE*n/(ms/(3.0*args.steps)*1e-3)/1e9/HBM_PEAK_GBS for ms in ms_samples]
-    # cross-check (separate pass): events around every single launch; ~3 % higher because of the event brackets
-    n_ev = min(args.steps, 50)
-    _, ms_kernel_each = dev.advance_timed(n_ev, per_launch=True)
     d = dev.diagnostics()
     assert np.isfinite(d).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *dev.get_state())
+    if args.full:
+        # the spread of the figure: the same K-step region four more times (the state keeps evolving, no host reset in between);
+        # `value`, `ms_per_step` and `roofline.frac` stay those of the FIRST region (the contract's timed K steps), the samples say
+        # how far one 2-3 ms region is from the next on this box (clock state, Infinity Cache contents)
+        ms_samples = [ms_events] + [dev.advance_timed(args.steps, per_launch=False)[0] for _ in range(4)]
+        frac_samples = [BYTES_PER_ELEMENT_UPDATE*n/(ms/(3.0*args.steps)*1e-3)/1e9/HBM_PEAK_GBS for ms in ms_samples]
+        # cross-check (separate pass): events around every single launch; ~3 % higher because of the event brackets
+        n_ev = min(args.steps, 50)
+        _, ms_kernel_each = dev.advance_timed(n_ev, per_launch=True)
+        assert np.isfinite(dev.diagnostics()).all()
     value = n*3.0*args.steps/t_wall
     achieved = BYTES_PER_ELEMENT_UPDATE*n/(ms_kernel*1e-3)/1e9
     fused = dev.fused_pair_info()
@@ -233,13 +263,12 @@ def run_single(args):
         'dtype': 'f64', 'data': 'synthetic',
         'config': {'workload': 'BASELINE cfg2: RectangleMesh(1000,500,100e3,50e3) = 1M triangles, DG-P1 SWE, SSPRK33, '
                                'flat h=20, closed walls, dt=0.25', 'n_cells': n, 'parallelism': 'single',
-                   'prewarm_s': args.prewarm},
+                   'prewarm_s': args.prewarm, 'full': bool(args.full)},
         'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      # `frac` keeps SURVEY.md 8d's definition: the bytes of THREE stage launches (228 B per element-update) over the
                      # time - a useful-work rate.  With stages fused the launches move fewer bytes than that model, so `frac` contains an
                      # algorithmic saving and could pass 1 as fusion deepens; the three figures after it say what the hardware did:
-                     'frac': achieved/HBM_PEAK_GBS, 'frac_samples': frac_samples, 'frac_median': float(np.median(frac_samples)),
-                     'frac_min': float(min(frac_samples)), 'frac_max': float(max(frac_samples)),
+                     'frac': achieved/HBM_PEAK_GBS,
                      'frac_definition': 'SURVEY 8d model bytes of three stage launches (684 B per triangle and step) / step time / 8 TB/s',
                      # (1) the bytes the launch structure that RAN must move in the same perfect-cache model (all three stages in one
                      #     launch: 180 B per triangle and step; fused pair + stage 3: 432; three stage launches: 684 = frac) over the time
@@ -263,12 +292,20 @@ def run_single(args):
                      'fused_stage_pair': {'tiles': fused[1], 'ring_cells': fused[2]} if (fused[0] and structure == 'pair') else None,
                      'fused_stage_triple': (dict(zip(('tiles', 'ring1_cells', 'ring2_cells'), dev.fused_triple_info()[1:]))
                                             if structure == 'triple' else None),
-                     'avg_launch_ms': ms_kernel, 'avg_launch_ms_per_launch_events': ms_kernel_each,
-                     # the mean duration of ONE launch by the per-launch events: what the launch-weighted mean of the kernel rows of
-                     # `rocprofv3 --kernel-trace --stats` of this command comes to (profiles/)
-                     'avg_kernel_launch_ms': ms_kernel_each*3.0/LAUNCHES[structure],
+                     'avg_launch_ms': ms_kernel,
                      'algorithmic_bytes_per_launch': BYTES_PER_ELEMENT_UPDATE*n},
     }
+    if not args.full:
+        dev.close()
+        print(json.dumps(out))
+        return
+    out['roofline'].update({
+        'frac_samples': frac_samples, 'frac_median': float(np.median(frac_samples)),
+        'frac_min': float(min(frac_samples)), 'frac_max': float(max(frac_samples)),
+        'avg_launch_ms_per_launch_events': ms_kernel_each,
+        # the mean duration of ONE launch by the per-launch events: what the launch-weighted mean of the kernel rows of
+        # `rocprofv3 --kernel-trace --stats` of this command comes to (profiles/)
+        'avg_kernel_launch_ms': ms_kernel_each*3.0/LAUNCHES[structure]})
     if not args.no_beyond_cache:
         out['roofline'].update(beyond_cache(args))
     if not args.no_cpu:
@@ -292,12 +329,21 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
-    ap.add_argument('--no-beyond-cache', action='store_true', help='skip the 4M-triangle run behind roofline.frac_beyond_cache')
+    ap.add_argument('--full', action='store_true',
+                    help='single GPU: after the headline figure also the spread of five timed regions, the per-launch events, the '
+                         '4M-triangle run and the CPU baseline (a multi-GPU run always reports its set-up)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='single GPU: write the state after the last timed step (a fixed sample of the cells) as DIR/*.npy')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--no-beyond-cache', action='store_true', help='with --full: skip the 4M-triangle run behind roofline.frac_beyond_cache')
     ap.add_argument('--prewarm', type=float, default=PREWARM_S, help='seconds of untimed stepping before the warm-up steps')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if args.gpus > 1 or world > 1 or os.environ.get('THETIS_AMD_FORCE_DIST'):   # env: exercise the N>1 code path on one GPU
+        if args.dump_outputs:
+            ap.error('--dump-outputs: single-GPU runs only')
         from tools.benchlib import run_distributed_bench
         case = build_case
         if os.environ.get('THETIS_AMD_BENCH_MESH'):       # tests: "nx,ny" - many ranks sharing the one GPU of a test box

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib, env):
     e = dict(os.environ)
     e.update(env)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '2', '--no-cpu', '--prewarm', '0.05']
-                       + (['--no-beyond-cache'] if env else []),
+                       + (['--no-beyond-cache'] if env else ['--full']),
                        capture_output=True, text=True, env=e, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -50,6 +51,31 @@ def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib, env):
         assert d['config']['volume_conserved'] is True
     if env:
         assert d['config']['failures'] == [] and 'p2p' in d['config']['transports_verified']
+
+
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_every_run(hip_lib, tmp_path):
+    """A plain single-GPU run (no --full) reports the timed region only; --dump-outputs writes the state after the last timed step,
+    and the timed steps start from the same state whatever the pre-warm did: two runs give the same bits."""
+    dumps = []
+    for i, prewarm in enumerate(('0.2', '0')):
+        out = tmp_path/('dump{:d}'.format(i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '3', '--prewarm',
+                            prewarm, '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+        assert d['steps'] == 5 and d['warmup'] == 3 and d['config']['full'] is False
+        assert abs(d['value'] - 1e6*3*5/(d['ms_per_step']*5e-3))/d['value'] < 1e-9
+        rf = d['roofline']
+        assert 'cpu_baseline' not in d and 'frac_samples' not in rf and 'frac_beyond_cache' not in rf and 'avg_kernel_launch_ms' not in rf
+        files = sorted(os.listdir(out))
+        assert files == ['cells.npy', 'eta.npy', 'uv.npy']
+        arrs = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 << 20
+        assert all(a.dtype == np.float64 for a in arrs.values()) and arrs['uv'].shape == (1 << 18, 3, 2) and arrs['eta'].shape == (1 << 18, 3)
+        assert np.isfinite(arrs['uv']).all() and np.isfinite(arrs['eta']).all()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_bench_two_ranks_through_torch_distributed_run(hip_lib):

@@ -3,8 +3,8 @@
 #   TAG=r06a STEPS="tests bench kstats pmc1m pmc4m cfgs ranks" bash tools/gpu_session.sh
 # leaves its files under gpurun_out/$TAG (copy what is to be judged into profiles/).  Steps:
 #   tests   the whole GPU suite (+ smoke)
-#   bench   the bench line as the driver runs it
-#   kstats  rocprofv3 --kernel-trace --stats of `bench.py --no-cpu --no-beyond-cache`: every row is the 1 M-cell workload
+#   bench   the full bench line (bench.py --full: spread, per-launch events, 4 M triangles, CPU baseline)
+#   kstats  rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu --no-beyond-cache`: every row is the 1 M-cell workload
 #   pmc1m   PMC passes of the library's launches at 1 M cells -> ${TAG}_traffic.json (+ VALU wave-instructions per step)
 #   pmc4m   the same at 4 M cells -> ${TAG}_traffic_4m.json
 #   cfgs    every row of tools/cfgbench.py
@@ -22,11 +22,11 @@ if has tests; then
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 fi
 if has bench; then
-  timeout 900 python bench.py > $O/${TAG}_bench_line.json 2> $O/bench.err; tail -1 $O/${TAG}_bench_line.json | cut -c1-1500
+  timeout 900 python bench.py --full > $O/${TAG}_bench_line.json 2> $O/bench.err; tail -1 $O/${TAG}_bench_line.json | cut -c1-1500
 fi
 if has kstats; then
   cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kstats -- python $R/bench.py --no-cpu --no-beyond-cache > $R/$O/kstats.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kstats -- python $R/bench.py --full --no-cpu --no-beyond-cache > $R/$O/kstats.log 2>&1
   cd $R
   cp $(ls $O/kstats/*/*kernel_stats.csv | head -1) $O/${TAG}_kernel_stats_1m.csv 2>/dev/null
   head -6 $O/${TAG}_kernel_stats_1m.csv | cut -c1-220
