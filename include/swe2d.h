@@ -495,6 +495,28 @@ int  swe2d_debug_flow_tear(swe2d_handle *h, int32_t block, int32_t microseconds,
 /* run on a caller-provided hipStream_t (e.g. torch's current stream) instead of the handle's own */
 int  swe2d_set_stream(swe2d_handle *h, void *hip_stream);
 
+/* ---- point probes: gauges / detectors (thetis/callback.py DetectorsCallback, Function.at) ------------------------------------
+ * A probe set holds M points, each a device cell (the handle's own numbering, as every cell argument here) and its nodes_per_cell
+ * nodal weights (barycentric on triangles, bilinear on quadrilaterals; the caller locates the points), and a list of fields:
+ * SWE2D_PROBE_UV (2 components), SWE2D_PROBE_ELEV (1) or a tracer id >= 0 (1).  A row is, per point, the components of the fields
+ * in list order: value = w0*v0 + w1*v1 + w2*v2 (+ w3*v3), left to right without contraction, v the nodal values of the state that
+ * swe2d_get_state / swe2d_tracer_get_state would return (wetting-drying: eta, not the displaced depth) - the same bits as that sum
+ * computed on the host from those arrays.  The rows are kept on the device (capacity rows); appending is one launch on the handle's
+ * stream, no synchronisation, so a row may be appended after every step of a batch.  Every probe call inside a stream capture
+ * returns SWE2D_ERR_UNSUPPORTED.  No reference counterpart at the C level (the reference interpolates onto a VertexOnlyMesh). */
+#define SWE2D_PROBE_UV   (-1)
+#define SWE2D_PROBE_ELEV (-2)
+int  swe2d_probe_create(swe2d_handle *h, int32_t n_points, const int32_t *cells, const double *weights, int32_t n_fields,
+                        const int32_t *fields, int32_t capacity, int32_t *probe_id);       /* weights: [n_points][nodes_per_cell] */
+int  swe2d_probe_width(swe2d_handle *h, int32_t probe_id, int32_t *n_points, int32_t *n_components, int32_t *capacity);
+/* one row of the current state (asynchronous); SWE2D_ERR_INVALID_ARGUMENT and nothing written when the set holds `capacity` rows */
+int  swe2d_probe_append(swe2d_handle *h, int32_t probe_id);
+/* the rows appended since the last read -> out [rows][n_points][n_components] (room for `capacity` rows), then the set is empty */
+int  swe2d_probe_read(swe2d_handle *h, int32_t probe_id, double *out, int32_t *n_rows);
+/* one row of the current state -> out [n_points][n_components], synchronously; the stored rows are not touched */
+int  swe2d_probe_eval(swe2d_handle *h, int32_t probe_id, double *out);
+int  swe2d_probe_destroy(swe2d_handle *h, int32_t probe_id);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ domain-decomposed as ``mpiexec -n N`` does it for the reference (thetis_amd/comm
 import os  # noqa: F401  (the reference's scripts use os.getenv after `from thetis import *`)
 
 from . import solver2d  # noqa: F401
+from .callback import DetectorsCallback, TimeSeriesCallback2D  # noqa: F401
+from .pointeval import PointNotInDomainError, select_and_move_detectors  # noqa: F401
 from .expr import *  # noqa: F401,F403  (SpatialCoordinate, conditional, as_vector, sin, cos, exp, sqrt, pi ...)
 from .function import Function, FunctionSpace, get_functionspace  # noqa: F401
 from .mesh import Mesh2d, PeriodicRectangleMesh, RectangleMesh, SquareMesh, UnitSquareMesh  # noqa: F401

@@ -25,6 +25,7 @@ ABI_VERSION = 12         # include/swe2d.h SWE2D_ABI_VERSION
  OPT_FLOW_POLL, OPT_FLOW_CAPACITY, OPT_FLOW_TIMEOUT_MS, OPT_P2P_TIMEOUT_MS, OPT_P2P_ZONE, OPT_ROCTX) = range(15)
 OPT_COUNT = 15
 SNAPSHOT_SLOTS = 2
+PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
 # The library itself never reads the environment (include/swe2d.h, swe2d_set_option).  As a convenience of THIS binding the variables
@@ -178,6 +179,12 @@ SYMBOLS = {
     'swe2d_debug_flow_tear': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'swe2d_set_stream': (ctypes.c_int, [_H, ctypes.c_void_p]),
     'swe2d_set_exchange_stream': (ctypes.c_int, [_H, ctypes.c_void_p]),
+    'swe2d_probe_create': (ctypes.c_int, [_H, ctypes.c_int32, _ip, _dp, ctypes.c_int32, _ip, ctypes.c_int32, _ip]),
+    'swe2d_probe_width': (ctypes.c_int, [_H, ctypes.c_int32, _ip, _ip, _ip]),
+    'swe2d_probe_append': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_probe_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip]),
+    'swe2d_probe_eval': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
+    'swe2d_probe_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
 }
 
 _lib = None

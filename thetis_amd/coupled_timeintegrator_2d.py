@@ -56,6 +56,7 @@ class DeviceTracerSSPRK33(object):
         self._uploaded = None
         self._device_ahead = False
         self.solution._pull_hook = self._pull
+        self.solution._device_field = (self, self.tid)
         self._src_signature = None
         self._push_source()
         if getattr(equation, 'conservative', False):
@@ -226,18 +227,27 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             if use_limiter:
                 self.device.tracer_limit(ts.tid)
 
-    def advance_steps(self, t, n_steps):
-        """``n_steps`` coupled steps without forcing updates; one library call when every stepper is SSPRK33."""
+    def advance_steps(self, t, n_steps, probes=None):
+        """``n_steps`` coupled steps without forcing updates; one library call when every stepper is SSPRK33.  ``probes``: probe
+        sets of the device that take one row after every step (FlowSolver2d.create_iterator)."""
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
         fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
         if not fused:
             for i in range(int(n_steps)):
                 self.advance(t + i*self.swe.dt)
+                for pid in probes or ():
+                    self.device.probe_append(pid)
             return
         self.swe._sync_to_device()
         for ts in self.tracers.values():
             ts._sync_to_device()
-        self.device.advance_coupled(int(n_steps), tracer_only=self.options.tracer_only, use_limiter=use_limiter)
+        if probes:
+            for _ in range(int(n_steps)):
+                self.device.advance_coupled(1, tracer_only=self.options.tracer_only, use_limiter=use_limiter)
+                for pid in probes:
+                    self.device.probe_append(pid)
+        else:
+            self.device.advance_coupled(int(n_steps), tracer_only=self.options.tracer_only, use_limiter=use_limiter)
         self.swe._device_ahead = True
         for ts in self.tracers.values():
             ts._device_ahead = True

@@ -516,6 +516,7 @@ void swe2d_destroy(swe2d_handle *hh)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->my_stream) (void)hipStreamSynchronize(h->my_stream);
+    probe_free_all(h);
     for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
     for (auto &t : h->tracers) {

@@ -223,6 +223,16 @@ struct Handle {
     int lim_nv = 0;
     int *lim_v2c_off = nullptr, *lim_v2c_cell = nullptr, *lim_vbf_off = nullptr, *lim_vbf_facet = nullptr, *lim_tv = nullptr;
     double *lim_mean = nullptr, *lim_qmin = nullptr, *lim_qmax = nullptr;
+    // point probes (swe2d_probe.hip): slot = probe id; a destroyed set leaves an empty slot
+    struct Probe {
+        bool live = false;
+        int n_points = 0, width = 0, capacity = 0, rows = 0;
+        int *cell = nullptr;                            // [n_points] device cells
+        double *weight = nullptr;                       // [n_points][npc]
+        double *out = nullptr;                          // [capacity + 1][n_points][width]: the last row is swe2d_probe_eval's
+        std::vector<int> fields;                        // SWE2D_PROBE_UV / SWE2D_PROBE_ELEV / tracer id
+    };
+    std::vector<Probe> probes;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -332,6 +342,8 @@ int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles =
 int flow_check(Handle *h);
 // ---- peer-to-peer halo (swe2d_api_p2p.hip)
 size_t p2p_channel_offset(const int *width, int c, int n_recv);
+// ---- point probes (swe2d_probe.hip): frees every probe set of the handle (swe2d_destroy)
+void probe_free_all(Handle *h);
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -12,3 +12,4 @@
 #include "swe2d_k_flow.hip"
 #include "swe2d_k_flow_wd.hip"
 #include "swe2d_k_tracer.hip"
+#include "swe2d_probe.hip"

@@ -570,6 +570,49 @@ class Swe2dDevice(object):
         a = np.ascontiguousarray(limbs, dtype=np.int64).reshape(_lib.SUM_LIMBS)
         return float(self.lib.swe2d_sum_limbs_to_double(a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
 
+    # -- point probes (gauges, Function.at): csrc/swe2d_probe.hip
+    _PROBE_FIELDS = {'uv': _lib.PROBE_UV, 'elev': _lib.PROBE_ELEV}
+
+    def probe_create(self, cells, weights, fields, capacity=0):
+        """A probe set of the points in ``cells`` (caller numbering) with their nodal ``weights`` (M, k) (thetis_amd/pointeval.py);
+        ``fields``: 'uv', 'elev' or a tracer id, in row order; ``capacity``: rows kept on the device.  Returns its id."""
+        cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+        dev = np.ascontiguousarray((cells if self.perm is None else self.inv_perm[cells]).astype(np.int32))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(len(cells), self.npc))
+        codes = np.ascontiguousarray([self._PROBE_FIELDS[f] if isinstance(f, str) else int(f) for f in fields], dtype=np.int32)
+        pid = ctypes.c_int32()
+        self._ck(self.lib.swe2d_probe_create(self.h, len(dev), _iptr(dev), _ptr(w), len(codes), _iptr(codes), int(capacity),
+                                             ctypes.byref(pid)))
+        return pid.value
+
+    def probe_shape(self, pid):
+        """(points, components per point, row capacity)"""
+        m, w, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._ck(self.lib.swe2d_probe_width(self.h, int(pid), ctypes.byref(m), ctypes.byref(w), ctypes.byref(c)))
+        return m.value, w.value, c.value
+
+    def probe_append(self, pid):
+        """one row of the current state, enqueued (no synchronisation)"""
+        self._ck(self.lib.swe2d_probe_append(self.h, int(pid)))
+
+    def probe_read(self, pid):
+        """the rows appended since the last read, (rows, points, components); the set is empty afterwards"""
+        m, w, c = self.probe_shape(pid)
+        out = np.empty((max(c, 1), m, w))
+        n = ctypes.c_int32()
+        self._ck(self.lib.swe2d_probe_read(self.h, int(pid), _ptr(out), ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def probe_eval(self, pid):
+        """(points, components) of the current state, synchronously"""
+        m, w, _ = self.probe_shape(pid)
+        out = np.empty((m, w))
+        self._ck(self.lib.swe2d_probe_eval(self.h, int(pid), _ptr(out)))
+        return out
+
+    def probe_destroy(self, pid):
+        self._ck(self.lib.swe2d_probe_destroy(self.h, int(pid)))
+
     # -- tracers + limiter
     def _nodal_in(self, a):
         a = np.asarray(a, dtype=np.float64).reshape(self.n_cells, self.npc)

@@ -102,6 +102,7 @@ class Function(object):
         self._data = np.zeros(shape)
         self._host_version = 0
         self._pull_hook = None          # set by a device time stepper: refreshes _data from HBM when stale
+        self._device_field = None       # set by a device time stepper: (stepper, probe field code) - point values without a pull
         self.dat = _Dat(self)
         if val is not None:
             self.assign(val)
@@ -255,8 +256,45 @@ class Function(object):
             return d.reshape((mesh.num_cells, k) + d.shape[1:])
         return np.repeat(d[:, None], k, axis=1)
 
-    def at(self, xy):
-        raise NotImplementedError('point evaluation is not part of the hot path')
+    def at(self, *points, **kwargs):
+        """Values at points (firedrake's Function.at): ``f.at((x, y))`` -> a scalar or a (2,) array, ``f.at([(x0, y0), ...])`` or
+        ``f.at(p0, p1, ...)`` -> an array over the points.  ``dont_raise=True``: None for a point outside the mesh instead of
+        PointNotInDomainError; ``tolerance``: in reference coordinates (thetis_amd/pointeval.py).  The solver's device-resident fields
+        are sampled on the device by a cached probe set (csrc/swe2d_probe.hip), without copying the state to the host; on several
+        ranks that call is collective."""
+        from . import pointeval
+        dont_raise = bool(kwargs.pop('dont_raise', False))
+        tolerance = kwargs.pop('tolerance', None)
+        if kwargs:
+            raise TypeError('unexpected keyword arguments {:}'.format(sorted(kwargs)))
+        arg = points[0] if len(points) == 1 else points
+        arr = np.asarray(arg, dtype=np.float64)
+        single = arr.ndim == 1
+        loc = pointeval.PointLocator(self._fs.mesh_obj, arr.reshape(-1, 2), tolerance=tolerance)
+        if not dont_raise:
+            loc.check()
+        found = loc.cells >= 0
+        vals = self._values_at(loc.cells[found], loc.weights[found])
+        out, j = [], 0
+        for ok in found:
+            if ok:
+                out.append(vals[j] if self._fs.vector else float(vals[j]))
+                j += 1
+            else:
+                out.append(None)
+        if single:
+            return out[0]
+        return np.array(out) if found.all() else out
+
+    def _values_at(self, cells, weights):
+        """(M[, 2]) values at located points: on the device for a device-resident field, else from the host copy"""
+        from . import pointeval
+        dev = self._device_field
+        if dev is not None and self._fs.family == 'DG' and self._fs.degree == 1:
+            vals = pointeval.probe_once(dev[0], dev[1], cells, weights)
+            if vals is not None:
+                return vals if self._fs.vector else vals[:, 0]
+        return pointeval.evaluate(self.cell_node_values(), cells, weights)
 
 
 def _evaluate(expr, xy, fs):

@@ -140,6 +140,8 @@ class ERKGenericShuOsher(TimeIntegrator):
         uv, eta = self.solution.subfunctions
         uv._pull_hook = self._pull_solution
         eta._pull_hook = self._pull_solution
+        uv._device_field = (self, 'uv')
+        eta._device_field = (self, 'elev')
 
     # ---- coefficient / boundary upload
     def _nodal(self, value, vector=False):
@@ -331,11 +333,18 @@ class ERKGenericShuOsher(TimeIntegrator):
             for i in range(self.n_stages):
                 self.solve_stage(i, t, update_forcings)
 
-    def advance_steps(self, t, n_steps):
+    def advance_steps(self, t, n_steps, probes=None):
         """``n_steps`` time steps without forcing updates in ONE call into the library (FlowSolver2d.iterate batches the
-        steps between exports: no Python between the launches)."""
+        steps between exports: no Python between the launches).  ``probes``: ids of probe sets of the device that take one row
+        after every step - then a step launch and the row launches alternate (enqueued, no synchronisation)."""
         self._sync_to_device()
-        self.device.advance(int(n_steps))
+        if probes:
+            for _ in range(int(n_steps)):
+                self.device.advance(1)
+                for pid in probes:
+                    self.device.probe_append(pid)
+        else:
+            self.device.advance(int(n_steps))
         self._last_stage = 2
         self._device_ahead = True
 
@@ -369,7 +378,13 @@ class ForwardEuler(ERKGenericShuOsher):
         self.device.advance_forward_euler(1)
         self._device_ahead = True
 
-    def advance_steps(self, t, n_steps):
+    def advance_steps(self, t, n_steps, probes=None):
         self._sync_to_device()
-        self.device.advance_forward_euler(int(n_steps))
+        if probes:
+            for _ in range(int(n_steps)):
+                self.device.advance_forward_euler(1)
+                for pid in probes:
+                    self.device.probe_append(pid)
+        else:
+            self.device.advance_forward_euler(int(n_steps))
         self._device_ahead = True

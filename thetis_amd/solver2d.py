@@ -362,6 +362,7 @@ class FlowSolver2d(object):
     def export(self, time=None):
         """Export all fields to disk and evaluate the export callbacks (solver2d.py:799-812)."""
         self.callbacks.evaluate(mode='export', index=self.i_export)
+        self.callbacks.export()
         for e in self.exporters.values():
             e.export(time=time)
 
@@ -446,7 +447,13 @@ class FlowSolver2d(object):
         if self.export_initial_state:
             self._export_now(export_func)
         stepper = self.timestepper
-        can_batch = (_batch and update_forcings is None and not self.callbacks['timestep'] and hasattr(stepper, 'advance_steps'))
+        step_cbs = [self.callbacks['timestep'][name] for name in sorted(self.callbacks['timestep'])]
+        # per-time-step callbacks keep the steps batched when every one of them is a device detector (callback.DetectorsCallback):
+        # the device appends a row after every step, the rows are handed over after the batch - the times and values of the
+        # step-by-step loop.  Anything else (a host callback, several ranks) takes the step-by-step loop.
+        batch_rows = bool(step_cbs) and self.comm.size == 1 and all(hasattr(cb, 'row_probe') for cb in step_cbs)
+        can_batch = (_batch and update_forcings is None and hasattr(stepper, 'advance_steps')
+                     and (not step_cbs or (batch_rows and all(cb.row_probe(1) is not None for cb in step_cbs))))
 
         def steps_to_next_event():
             """steps until the loop below would export or stop, by the loop's own arithmetic: t_k = t_start + k*dt"""
@@ -458,17 +465,33 @@ class FlowSolver2d(object):
                 n += 1
 
         while self.simulation_time <= o.simulation_end_time - eps:
+            probes = None
             if can_batch:
                 n = steps_to_next_event()
-                stepper.advance_steps(self.simulation_time, n)
+                if step_cbs:
+                    probes = [cb.row_probe(n) for cb in step_cbs]
+                    if any(p is None for p in probes):        # a host edit between the stages of a step: this batch step by step
+                        probes, n = None, 1
+                        stepper.advance(self.simulation_time, update_forcings)
+                    else:
+                        stepper.advance_steps(self.simulation_time, n, probes=[pid for _, pid in probes])
+                else:
+                    stepper.advance_steps(self.simulation_time, n)
             else:
                 n = 1
                 stepper.advance(self.simulation_time, update_forcings)
             yield self.simulation_time                  # the time the step STARTED from, as the reference's generator does
+            if probes is not None:
+                rows = [dev.probe_read(pid) for dev, pid in probes]
+                for k in range(n):                      # in the order the step-by-step loop evaluates them
+                    t_k = t_start + (n_done + k + 1)*self.dt
+                    for cb, r in zip(step_cbs, rows):
+                        cb.take_row(t_k, r[k])
             n_done += n
             self.iteration += n
             self.simulation_time = t_start + n_done*self.dt          # k*dt, never an accumulated sum (solver2d.py:1127)
-            self.callbacks.evaluate(mode='timestep')
+            if probes is None:
+                self.callbacks.evaluate(mode='timestep')
             if self.simulation_time >= export_due - eps:
                 self.i_export += 1
                 export_due += o.simulation_export_time

@@ -252,6 +252,39 @@ class PartitionedDevice(object):
         k = self.npc
         return out[:, :2*k].reshape(self.n_cells, k, 2), np.ascontiguousarray(out[:, 2*k:])
 
+    # ---- point probes (one-shot: partitioned runs sample from the per-step loop)
+    def probe_create(self, cells, weights, fields, capacity=0):
+        """``cells``: GLOBAL cells of the points (located on the global mesh by every rank).  A point belongs to the rank that owns
+        its cell, never to a ghost copy; this rank's handle probes its own points only.  Returns an id of this object."""
+        cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+        n_own = self.part.n_owned
+        local = np.full(self.n_cells, -1, dtype=np.int64)
+        local[self._g[:n_own]] = np.arange(n_own)
+        mine = np.nonzero(local[cells] >= 0)[0]
+        codes = [f if isinstance(f, str) else self._tid(f) for f in fields]
+        pid = None
+        if len(mine):
+            self.dist._check_exchange()
+            pid = self.dev.probe_create(local[cells[mine]], np.asarray(weights)[mine], codes)
+        if not hasattr(self, '_probes'):
+            self._probes = []
+        width = sum(2 if f == 'uv' else 1 for f in fields)
+        self._probes.append((pid, mine, len(cells), width))
+        return len(self._probes) - 1
+
+    def probe_eval(self, i):
+        """(points, components) of the current state on every rank.  COLLECTIVE."""
+        pid, mine, m, width = self._probes[i]
+        self.dist.synchronize()
+        rows = self.dev.probe_eval(pid) if pid is not None else np.zeros((0, width))
+        return self.comm.gather_rows(mine, rows, m)
+
+    def probe_destroy(self, i):
+        pid = self._probes[i][0]
+        if pid is not None:
+            self.dev.probe_destroy(pid)
+        self._probes[i] = (None, np.zeros(0, dtype=np.int64), 0, 0)
+
     def diagnostics(self):
         return self.dist.diagnostics()
 
