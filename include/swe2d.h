@@ -173,16 +173,18 @@ int  swe2d_fused_set_order(swe2d_handle *h, const int32_t *cells_in_tile_order);
  * stage 2 on interior + the first).  Same results bit for bit. */
 int  swe2d_fused_triple_info(swe2d_handle *h, int32_t out[4]);
 /* The two-ring tiles alone may be cut from an order of their own, with positions at which a tile must begin (tile_starts, n_starts
- * of them; NULL / 0: none): compact patches sized for interior + two rings (thetis_amd/ordering.py triple_tile_order: 12 x 7 quads of
+ * of them; NULL / 0: none): compact patches sized for interior + two rings (thetis_amd/ordering.py triple_tile_order: 11 x 8 quads of
  * a RectangleMesh) instead of as many consecutive cells as fit.  cells_in_tile_order = NULL: the order of swe2d_fused_set_order.
  * Results do not depend on it.  Replaces nothing in the reference (Firedrake's PyOP2 has no tiling to steer). */
 int  swe2d_fused_set_triple_tiles(swe2d_handle *h, const int32_t *cells_in_tile_order, const int32_t *tile_starts, int32_t n_starts);
 /* A PARTITION's whole step in one launch (round 6, last): stage 3 on cells [0, cell_end), the last of the step's three shrinking ranges
  * (thetis_amd/partition.py stage_range); stages 1 and 2 are evaluated on the tiles' supersets of theirs and never leave the chip.  The
  * result goes to the second state buffer and the two change places: inside a stream capture call it an EVEN number of times per
- * captured sequence (the pointers a replay uses are those of the capture; an odd number is reported as SWE2D_ERR_UNSUPPORTED by the
- * next swe2d_synchronize / swe2d_get_stage_state / swe2d_solve_step_cells outside the capture), and build the tables before
- * (swe2d_fused_step_info).
+ * captured sequence (the pointers a replay uses are those of the capture).  The count is kept per capture: a capture with an odd
+ * number is reported as SWE2D_ERR_UNSUPPORTED, once, by the next call outside a capture that reads or writes the state (that call does
+ * nothing else), and its host-side swap is undone - the state is then the one from before the capture, which ran nothing.  Build the
+ * tables before (swe2d_fused_step_info): inside a capture swe2d_fused_step_info / swe2d_fused_triple_info allocate nothing and answer
+ * out[0] = 0 while the tables are not built.
  * Cells of the state beyond cell_end hold stale values afterwards (ghost cells the next exchange rewrites).  SWE2D_ERR_UNSUPPORTED
  * where the kernel does not cover the handle (quadrilaterals, wetting-drying, viscosity, source terms unless forced).
  * swe2d_fused_step_info: out[0] = 1 when the caller should take it (patches handed in with swe2d_fused_set_triple_tiles and more
@@ -219,8 +221,11 @@ int  swe2d_get_state(swe2d_handle *h, double *uv, double *eta);
 /* the stage solution the reference assigns to `solution` after solve_stage(i_stage) (rungekutta.py:930-946): i_stage 0, 1 read
  * the buffers holding U1, U2; i_stage 2 (= swe2d_get_state) the step result.  The reference's stage_sol[i] always is what stage i
  * left; here the fused stage pair keeps U1, the dataflow kernel U1 and U2, on chip: when the step made last did not leave the asked
- * stage solution in memory (or no stage has run since swe2d_set_state / a restore) the call returns SWE2D_ERR_UNSUPPORTED - drive
- * the step with swe2d_solve_stage to read intermediate stages */
+ * stage solution in memory (or no stage has run since swe2d_set_state / a restore, or the step made last was a ForwardEuler step,
+ * or a swap of the state buffers) the call returns SWE2D_ERR_UNSUPPORTED - drive the step with swe2d_solve_stage to read
+ * intermediate stages.  Stage launches made inside a stream capture execute nothing when they are recorded and the host never sees
+ * their replays: after any state-writing launch recorded in a capture, i_stage 0 and 1 are refused (before and after a replay) until
+ * the next eager step writes them again.  i_stage 2 reads buffer A, which a replay writes in place. */
 int  swe2d_get_stage_state(swe2d_handle *h, int i_stage, double *uv, double *eta);
 /* Save (restore = 0) / bring back (restore = 1) the time-stepping state - the step result and every tracer - in a device-side
  * copy, exactly, without the host: for steps that have to be undone (graph capture warm-ups, verification replays, benchmarks).
@@ -276,7 +281,12 @@ int  swe2d_set_scalar(swe2d_handle *h, int which, double value);
 int  swe2d_set_wetting_and_drying(swe2d_handle *h, int enable, const double *alpha_vertex);
 
 /* ERKGenericShuOsher.advance (rungekutta.py:949-952) repeated n_steps times, forcings constant in time.
- * Asynchronous: returns after enqueueing. */
+ * Asynchronous: returns after enqueueing.
+ * Buffer A: every step path leaves the step result in state buffer A (what swe2d_get_state reads and the next step starts from),
+ * whatever the launches were.  The three-stage kernel writes U(3) into buffer B and swaps the host's pointers to A and B; inside a
+ * stream capture swe2d_advance never takes it (a graph replays the pointers of its capture), so a captured swe2d_advance always ends
+ * on the buffer it began on and can be replayed any number of times.  A capture that swapped an odd number of times
+ * (swe2d_solve_step_cells) has its swap undone when it is reported, see swe2d_solve_step_cells. */
 int  swe2d_advance(swe2d_handle *h, int n_steps);
 /* ERKGenericShuOsher.solve_stage(i_stage) (rungekutta.py:930-946); i_stage = 0,1,2 in order. */
 int  swe2d_solve_stage(swe2d_handle *h, int i_stage);
@@ -384,7 +394,8 @@ int  swe2d_tracer_diagnostics(swe2d_handle *h, int tracer_id, double out[4]);
 /* limb sums (see swe2d_diagnostics_limbs) of { int T*H dx, int T dx } + { min, max } of the owned cells */
 int  swe2d_tracer_diagnostics_limbs(swe2d_handle *h, int tracer_id, int64_t limbs[12], double minmax[2]);
 /* GeneralCoupledTimeIntegrator2D.advance (coupled_timeintegrator_2d.py:93-113) x n_steps: SWE step (unless tracer_only),
- * then every tracer with the updated velocity, then the limiter (once per step) */
+ * then every tracer with the updated velocity, then the limiter (once per step).  Buffer A as for swe2d_advance: the shallow-water
+ * step result ends in state buffer A (the tracer stages read the velocity from there) and every tracer's result in its buffer A. */
 int  swe2d_advance_coupled(swe2d_handle *h, int n_steps, int tracer_only, int use_limiter);
 
 /* profiling aid: n_times streaming copies of the 9 state planes (9*stride doubles read + written, 8 B per lane) to calibrate

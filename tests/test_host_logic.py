@@ -405,6 +405,53 @@ def test_triple_tile_order_gives_patches_that_fill_a_workgroup():
     assert ordering.triple_tile_order(delaunay_case(n_points=400, seed=5)[0]) is None
 
 
+def test_malformed_option_switch_warns_and_keeps_the_library_rule(monkeypatch):
+    """A THETIS_AMD_* switch whose value does not convert (THETIS_AMD_P2P_ZONE outside its three names, a number that is none) is
+    reported with a warning and left out - the handle keeps the library's own rule - instead of raising in every device constructor;
+    the well-formed switches next to it still count."""
+    import warnings
+    from thetis_amd import _lib
+    for name in _lib.OPTION_ENV:
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv('THETIS_AMD_P2P_ZONE', 'nowhere')
+    monkeypatch.setenv('THETIS_AMD_FLOW', 'yes')
+    monkeypatch.setenv('THETIS_AMD_FUSE12', '2')
+    with pytest.warns(UserWarning) as rec:
+        opts = dict(_lib.options_from_environment())
+    text = ' '.join(str(w.message) for w in rec)
+    assert 'THETIS_AMD_P2P_ZONE' in text and 'THETIS_AMD_FLOW' in text, text
+    assert opts == {_lib.OPT_FUSED_STAGES: 2}
+    monkeypatch.setenv('THETIS_AMD_P2P_ZONE', 'finegrained')
+    monkeypatch.setenv('THETIS_AMD_FLOW', '0')
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')
+        opts = dict(_lib.options_from_environment())
+    assert opts == {_lib.OPT_FUSED_STAGES: 2, _lib.OPT_FLOW: 0, _lib.OPT_P2P_ZONE: 2}
+
+
+@pytest.mark.parametrize('value', ['11x8', 'a,b', '11', '11,8,2', '0,8', '-3,8', ' , '])
+def test_malformed_triple_tile_switch_warns_and_takes_the_default(monkeypatch, value):
+    """THETIS_AMD_TRIPLE_TILE = "bx,by" (an A/B switch of the two-ring patches, read by Swe2dDevice and DistributedSwe2d): a value
+    that is not two positive integers is reported with a warning and the default 11 x 8 patches are cut."""
+    from thetis_amd import ordering
+    monkeypatch.setenv('THETIS_AMD_TRIPLE_TILE', value)
+    with pytest.warns(UserWarning, match='THETIS_AMD_TRIPLE_TILE'):
+        assert ordering.triple_tile_shape() == (11, 8)
+
+
+def test_triple_tile_switch_values(monkeypatch):
+    import warnings
+    from thetis_amd import ordering
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')
+        monkeypatch.delenv('THETIS_AMD_TRIPLE_TILE', raising=False)
+        assert ordering.triple_tile_shape() == (11, 8)
+        monkeypatch.setenv('THETIS_AMD_TRIPLE_TILE', '0')
+        assert ordering.triple_tile_shape() is None
+        monkeypatch.setenv('THETIS_AMD_TRIPLE_TILE', '12,7')
+        assert ordering.triple_tile_shape() == (12, 7)
+
+
 def test_compact_connectivity_records_round_trip(tmp_path):
     """thetis_amd/csrc/swe2d_conn.h: the 16-B connectivity records the triangle kernels read.  Host packing against the kernels'
     unpacking (the same header compiled with g++): random records of every span, markers, the edges of the 19-bit range, and that

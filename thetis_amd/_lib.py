@@ -6,6 +6,7 @@ visible ``swe2d_create`` fails with SWE2D_ERR_NO_DEVICE - the product never comp
 """
 import ctypes
 import os
+import warnings
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('THETIS_AMD_LIB') or os.path.join(_HERE, 'libswe2d_hip.so')   # env: kernel A/B experiments
@@ -51,12 +52,16 @@ OPTION_ENV = {
 
 
 def options_from_environment():
-    """[(option, value)] for the variables of OPTION_ENV that are set."""
+    """[(option, value)] for the variables of OPTION_ENV that are set.  A value the conversion does not accept is reported with a
+    warning and left out: the option keeps the library's own rule (an A/B switch must not stop every device constructor)."""
     out = []
     for name, (opt, conv) in OPTION_ENV.items():
         v = os.environ.get(name)
         if v is not None and v != '':
-            out.append((opt, int(conv(v))))
+            try:
+                out.append((opt, int(conv(v))))
+            except (ValueError, KeyError, TypeError) as e:
+                warnings.warn('{}={!r} is not a valid value ({}: {}): the library\'s own rule applies'.format(name, v, type(e).__name__, e))
     return out
 
 

@@ -21,6 +21,24 @@ int fail(Handle *h, int code, const std::string &msg)
     return code;
 }
 
+bool stream_capturing(Handle *h, unsigned long long *id)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    unsigned long long cid = 0;
+    const bool yes = h->stream && hipStreamGetCaptureInfo(h->stream, &cs, &cid) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    if (id) *id = yes ? cid : 0;
+    return yes;
+}
+
+// Which stage solutions swe2d_get_stage_state may hand out.  A launch inside a stream capture executes nothing: the buffers keep what
+// they held, and a replay later writes them without the host knowing - both stage solutions are refused until an eager step.
+void stage_written(Handle *h, bool s0, bool s1)
+{
+    if (stream_capturing(h)) s0 = s1 = false;
+    h->stage_valid[0] = s0; h->stage_valid[1] = s1;
+}
+
 void fill_stage_args(Handle *h, SweStageArgs &a, int in, int u0, int out, double a0, double a1, double beta, int c0, int c1)
 {
     a.uin = h->state[in];
@@ -114,7 +132,8 @@ int launch_stage(Handle *h, int in, int u0, int out, double a0, double a1, doubl
     SWE_CHK_SYNC(h->stream);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SWE_BLOCK), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
-    if (out == 1 || out == 2) h->stage_valid[out - 1] = true;      // a stage launch leaves its stage solution in its buffer
+    if (out == 1 || out == 2)                                      // a stage launch leaves its stage solution in its buffer
+        stage_written(h, out == 1 || h->stage_valid[0], out == 2 || h->stage_valid[1]);
     if (h->visc) {
         // HorizontalViscosityTerm: U_out[uv] += beta*dt*M^-1 R_visc(U_in) on the same cells (swe2d_sipg.h)
         SweSipgArgs v{};
@@ -555,6 +574,7 @@ int swe2d_set_state(swe2d_handle *hh, const double *uv, const double *eta)
     Handle *h = H(hh);
     if (!h || !uv || !eta) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;       // (an odd capture's swap is undone before the new state lands)
     const size_t n = (size_t)h->n_cells*h->npc;
     HIP_TRY(h, hipMemcpyAsync(h->stage_uv, uv, 2*n*sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->stage_eta, eta, n*sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -588,6 +608,7 @@ int swe2d_state_snapshot_slot(swe2d_handle *hh, int slot, int restore)
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (slot < 0 || slot >= SWE2D_SNAPSHOT_SLOTS) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_state_snapshot: no such slot");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     Handle::Snapshot &sn = h->snapshot[slot];
     const size_t nb = (size_t)3*h->npc*h->stride*sizeof(double), nt = (size_t)h->npc*h->stride*sizeof(double);
     const size_t total = nb + h->tracers.size()*nt;
@@ -864,6 +885,7 @@ int swe2d_solve_stage_cells(swe2d_handle *hh, int i_stage, int32_t cell_begin, i
     if (cell_begin < 0 || cell_end > h->n_cells || cell_begin > cell_end)
         return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell range");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     static const char *names[3] = {"swe2d_solve_stage[0]", "swe2d_solve_stage[1]", "swe2d_solve_stage[2]"};
     RoctxRange range(h, names[(i_stage >= 0 && i_stage < 3) ? i_stage : 0]);
     return stage_on_range(h, i_stage, cell_begin, cell_end);
@@ -889,6 +911,7 @@ int swe2d_advance(swe2d_handle *hh, int n_steps)
     if (h->n_owned != h->n_cells)
         return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_advance on a partition: drive stages + halo exchange from the host");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance");
     // Up to 128 steps per launch without grid barriers (swe2d_flow.h) where every 64-cell block of the mesh is resident at once
     // (<= 131 k cells) and the kernel covers the configuration.  Same box, us/step, three stage launches per step -> flow launches:
@@ -920,11 +943,13 @@ int swe2d_advance_forward_euler(swe2d_handle *hh, int n_steps)
     if (!h || n_steps < 0) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad n_steps");
     if (h->n_owned != h->n_cells) return fail(h, SWE2D_ERR_UNSUPPORTED, "ForwardEuler is not available on partitions");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     for (int it = 0; it < n_steps; it++) {
         // U_new = U + dt M^-1 R(U): stage 0 of the Shu-Osher form; the result becomes buffer A by a pointer swap
         int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, 0, h->n_owned);
         if (rc) return rc;
         std::swap(h->state[0], h->state[1]);
+        h->stage_valid[0] = h->stage_valid[1] = false;     // buffer B now holds the state before the step, not a stage solution
     }
     return SWE2D_OK;
 }
@@ -938,13 +963,17 @@ int swe2d_forward_euler_cells(swe2d_handle *hh, int32_t cell_begin, int32_t cell
     if (cell_begin < 0 || cell_end > h->n_cells || cell_begin > cell_end)
         return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell range");
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, cell_begin, cell_end);
+    if (int rc = capture_parity_check(h)) return rc;
+    if (int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, cell_begin, cell_end)) return rc;
+    h->stage_valid[0] = h->stage_valid[1] = false;         // a ForwardEuler step leaves no SSPRK33 stage solution
+    return SWE2D_OK;
 }
 
 int swe2d_swap_state_buffers(swe2d_handle *hh)
 {
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (int rc = capture_parity_check(h)) return rc;
     std::swap(h->state[0], h->state[1]);
     h->stage_valid[0] = h->stage_valid[1] = false;
     return SWE2D_OK;
@@ -957,6 +986,7 @@ int swe2d_advance_timed(swe2d_handle *hh, int n_steps, int per_launch, float *ms
     if (h->n_owned != h->n_cells)
         return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_advance_timed on a partition is not supported");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     if (!per_launch) {
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         int rc = swe2d_advance(hh, n_steps);
@@ -1014,6 +1044,7 @@ int swe2d_tendency(swe2d_handle *hh, double *k_uv, double *k_eta)
     Handle *h = H(hh);
     if (!h || !k_uv || !k_eta) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     // k into buffer B: U_out = 1*k + 0*U0 + 0*U_in
     int rc = launch_stage(h, 0, 0, 1, 0.0, 0.0, 1.0, 0, h->n_owned);
     if (rc) return rc;

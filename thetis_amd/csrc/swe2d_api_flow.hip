@@ -297,6 +297,7 @@ int swe2d_solve_flow(swe2d_handle *hh, int32_t n_stages, const int32_t *cell_end
     Handle *h = H(hh);
     if (!h || !cell_end) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_solve_flow");
     return launch_flow(h, n_stages, cell_end);
 }
@@ -306,6 +307,7 @@ int swe2d_solve_flow_exchange(swe2d_handle *hh, int32_t n_cycles, int32_t stages
     Handle *h = H(hh);
     if (!h || !cell_end || n_cycles < 1) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_solve_flow_exchange");
     return launch_flow(h, stages_per_cycle, cell_end, n_cycles);
 }

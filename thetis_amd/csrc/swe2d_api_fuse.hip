@@ -160,7 +160,7 @@ int launch_fuse12(Handle *h, int cell_end)
     SWE_CHK_SYNC(h->stream);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SWE_FUSE_WG), 0, h->stream, q);
     HIP_TRY(h, hipGetLastError());
-    h->stage_valid[0] = false; h->stage_valid[1] = true;    // U(1) never left the chip; buffer C holds U(2)
+    stage_written(h, false, true);                          // U(1) never left the chip; buffer C holds U(2)
     return SWE2D_OK;
 }
 
@@ -276,7 +276,7 @@ int launch_fuse12_quad(Handle *h, int cell_end)
     SWE_CHK_SYNC(h->stream);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SWE_FUSE_WG), 0, h->stream, q);
     HIP_TRY(h, hipGetLastError());
-    h->stage_valid[0] = false; h->stage_valid[1] = true;
+    stage_written(h, false, true);
     return SWE2D_OK;
 }
 
@@ -294,11 +294,12 @@ fuse3_kernel_t pick_fuse3_kernel(bool nl, bool lf, bool src) { return src ? pick
 
 // Tiles: consecutive cells of the tile order as long as interior + ring 1 (facet neighbours of the interior) + ring 2 (facet
 // neighbours of ring 1) fit the 256 lanes and ring 2's facets towards the outside fit the staging area - and up to the next
-// position the caller marked as the start of a tile (swe2d_fused_set_triple_tiles: patches of 12 x 7 quads = 168 triangles + 38 + 42
-// fill 248 lanes, where 147 consecutive cells of the 16 x 6 numbering leave ragged patches with rings of 52 + 57).
+// position the caller marked as the start of a tile (swe2d_fused_set_triple_tiles: patches of 11 x 8 quads = 176 triangles + 38 + 42
+// fill the 256 lanes, where 147 consecutive cells of the 16 x 6 numbering leave ragged patches with rings of 52 + 57).
+// Allocations and copies: not inside a stream capture - there it builds nothing (fuse3_tile stays null) and the caller goes without.
 int fuse123_build(Handle *h)
 {
-    if (h->fuse3_tile) return SWE2D_OK;
+    if (h->fuse3_tile || stream_capturing(h)) return SWE2D_OK;
     const int n = h->n_cells;
     const size_t S = h->stride;
     const int *nbr = h->h_nbr.data();
@@ -387,7 +388,9 @@ int fuse123_build(Handle *h)
 // a whole step: state buffer A (U(0)) -> state buffer B (U(3)), then the two change places
 int launch_fuse123(Handle *h, int cell_end)
 {
+    if (int rc = capture_parity_check(h)) return rc;          // (an earlier capture's count is settled before this launch swaps)
     if (int rc = fuse123_build(h)) return rc;
+    if (!h->fuse3_tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stages: no tile tables (not built inside a stream capture)");
     SweFuse3Args q;
     fill_stage_args(h, q.st, 0, 0, 1, 0.0, 1.0, kBeta[0], 0, h->n_owned);
     q.st.idxc = h->opt[SWE2D_OPT_COMPACT_IDX] == 0 ? nullptr : h->idxc;
@@ -404,27 +407,35 @@ int launch_fuse123(Handle *h, int cell_end)
     HIP_TRY(h, hipGetLastError());
     std::swap(h->state[0], h->state[1]);
     h->stage_valid[0] = h->stage_valid[1] = false;          // U(1) and U(2) never left the chip
-    {   // inside a stream capture the swap is only the host's: a graph that holds an odd number of them ends on the other buffer than
-        // it began on and cannot be replayed twice - counted here, reported by capture_parity_check at the next call outside the capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) h->capture_swaps++;
-        (void)hipGetLastError();
+    // inside a stream capture the swap is only the host's: a graph that holds an odd number of them ends on the other buffer than it
+    // began on and cannot be replayed twice - counted per capture here, reported by capture_parity_check at the next call outside it
+    unsigned long long id = 0;
+    if (stream_capturing(h, &id)) {
+        if (id != h->capture_id) { h->capture_id = id; h->capture_swaps = 0; }   // (an earlier capture's count was settled above)
+        h->capture_swaps++;
     }
     return SWE2D_OK;
 }
 
+// Called on entry by every function that reads or writes the state buffers.  Once the capture that swapped has ended (no capture, or
+// another one) an odd count is settled: the host swap is undone - nothing ran, buffer A still holds the state from before the capture -
+// and the next call outside a capture returns SWE2D_ERR_UNSUPPORTED, once, without doing anything.
 int capture_parity_check(Handle *h)
 {
-    if (h->capture_swaps == 0) return SWE2D_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return SWE2D_OK; }
-    (void)hipGetLastError();
-    const int swaps = h->capture_swaps;
-    h->capture_swaps = 0;
-    if (swaps & 1)
-        return fail(h, SWE2D_ERR_UNSUPPORTED, "a stream capture recorded an odd number of swe2d_solve_step_cells launches: the graph ends on the other "
-                    "state buffer than it began on and cannot be replayed; capture an even number per sequence");
-    return SWE2D_OK;
+    if (h->capture_swaps == 0 && h->capture_odd == 0) return SWE2D_OK;
+    unsigned long long id = 0;
+    const bool capturing = stream_capturing(h, &id);
+    if (h->capture_swaps) {
+        if (capturing && id == h->capture_id) return SWE2D_OK;
+        if (h->capture_swaps & 1) { std::swap(h->state[0], h->state[1]); h->capture_odd++; }
+        h->capture_swaps = 0;
+    }
+    if (capturing || h->capture_odd == 0) return SWE2D_OK;
+    const int odd = h->capture_odd;
+    h->capture_odd = 0;
+    return fail(h, SWE2D_ERR_UNSUPPORTED, std::to_string(odd) + " stream capture(s) recorded an odd number of swe2d_solve_step_cells launches: "
+                "such a graph ends on the other state buffer than it began on and cannot be replayed (the state is the one from before the "
+                "capture); capture an even number per sequence");
 }
 
 // All three stages in one launch.  With tiles cut as consecutive cells of the numbering (147 + 52 + 57 per tile, ragged) the second ring
@@ -453,10 +464,7 @@ int step_swe(Handle *h)
 {
     if (fuse123_wanted(h)) {
         // all three stages in one launch (whole meshes; the launch swaps two state buffers on the host: not inside a stream capture)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-        (void)hipGetLastError();
-        if (!capturing) return launch_fuse123(h, h->n_owned);
+        if (!stream_capturing(h)) return launch_fuse123(h, h->n_owned);
     }
     if (fuse12_covers(h)) { if (int rc = fuse12_build(h)) return rc; }
     if (fuse12_covers(h) && (h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr)) {
@@ -543,6 +551,7 @@ int swe2d_fused_triple_info(swe2d_handle *hh, int32_t out[4])
     if (!fuse123_wanted(h)) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = fuse123_build(h)) return rc;
+    if (!h->fuse3_tile) return SWE2D_OK;                      // not built (inside a stream capture)
     out[0] = 1; out[1] = h->fuse3_n_tiles; out[2] = (int32_t)h->fuse3_ring1; out[3] = (int32_t)h->fuse3_ring2;
     return SWE2D_OK;
 }
@@ -566,6 +575,7 @@ int swe2d_fused_step_info(swe2d_handle *hh, int32_t out[4])
     if (mode != 3 && ((int)h->fuse3_start.size() != h->n_cells || h->n_cells <= 131072)) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = fuse123_build(h)) return rc;
+    if (!h->fuse3_tile) return SWE2D_OK;                      // not built (inside a stream capture): the caller takes the stage launches
     out[0] = 1; out[1] = h->fuse3_n_tiles; out[2] = (int32_t)h->fuse3_ring1; out[3] = (int32_t)h->fuse3_ring2;
     return SWE2D_OK;
 }
@@ -583,10 +593,7 @@ int swe2d_solve_step_cells(swe2d_handle *hh, int32_t cell_end)
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     if (!h->fuse3_tile) {           // tile tables: allocations and copies, not inside a stream capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-        (void)hipGetLastError();
-        if (capturing) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: first call inside a stream capture (swe2d_fused_step_info builds the tables)");
+        if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: first call inside a stream capture (swe2d_fused_step_info builds the tables)");
     }
     return launch_fuse123(h, cell_end);
 }
@@ -600,6 +607,7 @@ int swe2d_solve_stage_pair_cells(swe2d_handle *hh, int32_t cell_end_0, int32_t c
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (cell_end_1 < 0 || cell_end_1 > cell_end_0 || cell_end_0 > h->n_cells) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell ranges");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     if (fuse12_covers(h)) { if (int rc = fuse12_build(h)) return rc; }
     if (fuse12_covers(h) && (h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr)) return launch_fuse12(h, cell_end_1);
     if (int rc = stage_on_range(h, 0, 0, cell_end_0)) return rc;

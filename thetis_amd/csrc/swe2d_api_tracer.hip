@@ -579,6 +579,7 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
     if (!h || n_steps < 0) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad n_steps");
     if (h->n_owned != h->n_cells) return fail(h, SWE2D_ERR_UNSUPPORTED, "on a partition the host drives the coupled step (stages on cell ranges + halo exchanges, thetis_amd/distributed.py)");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance_coupled");
     for (int it = 0; it < n_steps; it++) {
         // the shallow-water step as swe2d_advance makes it on a mesh beyond the dataflow kernel: fused stage pair + stage 3 where

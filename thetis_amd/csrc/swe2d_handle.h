@@ -33,6 +33,15 @@ std::mutex g_chk_mutex;
 std::map<unsigned long long, unsigned long long> g_chk_allocs;       // base -> end
 bool g_chk_dirty = true;
 unsigned long long g_chk_launches = 0;
+void swe_chk_upload_locked()
+{
+    static SweChkTable t;
+    t.n = 0;
+    for (auto &kv : g_chk_allocs) if (t.n < SWE_CHK_MAX) { t.lo[t.n] = kv.first; t.hi[t.n] = kv.second; t.n++; }
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(swe_chk_tab), &t, sizeof(t));
+    g_chk_dirty = false;
+}
 hipError_t swe_chk_malloc(void **p, size_t n)
 {
     const hipError_t e = hipMalloc(p, n);
@@ -40,7 +49,9 @@ hipError_t swe_chk_malloc(void **p, size_t n)
         std::lock_guard<std::mutex> lock(g_chk_mutex);
         const char *st = getenv("THETIS_AMD_RANGE_SELFTEST");                  // negative control: record half of every allocation
         g_chk_allocs[(unsigned long long)*p] = (unsigned long long)*p + ((st && atoi(st)) ? n/2 : n);
-        g_chk_dirty = true;
+        // the table goes to the device now: the next checked launch may be recorded in a stream capture, where it cannot be
+        // copied, and the replays would check against a table without this allocation (the library never allocates inside one)
+        swe_chk_upload_locked();
     }
     return e;
 }
@@ -57,12 +68,7 @@ void swe_chk_sync(hipStream_t stream)
     if (!g_chk_dirty) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return;
-    static SweChkTable t;
-    t.n = 0;
-    for (auto &kv : g_chk_allocs) if (t.n < SWE_CHK_MAX) { t.lo[t.n] = kv.first; t.hi[t.n] = kv.second; t.n++; }
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(swe_chk_tab), &t, sizeof(t));
-    g_chk_dirty = false;
+    swe_chk_upload_locked();
 }
 }
 #define hipMalloc(p, n) swe_chk_malloc(p, n)
@@ -116,8 +122,14 @@ struct Handle {
     Handle() { for (int i = 0; i < SWE2D_OPT_COUNT; i++) opt[i] = -1; }
     // which of the stage buffers hold the stage solutions of the step made last (swe2d_get_stage_state): the fused and the dataflow
     // kernels keep U(1) (and U(2)) on chip
+    // (a launch inside a stream capture runs nothing: it clears both, see stage_written)
     bool stage_valid[2] = {false, false};
-    int capture_swaps = 0;                              // buffer swaps made while the stream was capturing (launch_fuse123): must be even per captured sequence
+    // buffer swaps made while the stream was capturing (launch_fuse123): must be even per captured sequence.  Counted per capture
+    // (capture_id, the id hipStreamGetCaptureInfo gives); a capture that ended on an odd count has its host swap undone and is
+    // counted in capture_odd until capture_parity_check reports it outside a capture
+    int capture_swaps = 0;
+    unsigned long long capture_id = 0;
+    int capture_odd = 0;
     int4 *idx4 = nullptr;                               // packed triangle connectivity (stage kernel), see SweStageArgs
     int2 *idx2 = nullptr;
     int4 *idxc = nullptr;                               // ... in 16 B (swe_conn_pack), what the stage kernels read (SWE2D_OPT_COMPACT_IDX)
@@ -325,6 +337,8 @@ bool fuse123_wanted(const Handle *h);
 int fuse123_build(Handle *h);
 int launch_fuse123(Handle *h, int cell_end);
 int capture_parity_check(Handle *h);                    // SWE2D_ERR_UNSUPPORTED once after a capture that swapped the state buffers an odd number of times
+bool stream_capturing(Handle *h, unsigned long long *id = nullptr);   // is the handle's stream capturing (and which capture)?
+void stage_written(Handle *h, bool s0, bool s1);        // a launch left U(1) / U(2) in buffers B / C (none of it inside a capture)
 int step_swe(Handle *h);                               // one SSPRK33 step of the shallow-water state on the whole mesh: fused pair + stage 3, or stage launches
 void fill_stage_args(Handle *h, SweStageArgs &a, int in, int u0, int out, double a0, double a1, double beta, int c0, int c1);
 int launch_stage(Handle *h, int in, int u0, int out, double a0, double a1, double beta, int c0, int c1);

@@ -150,15 +150,14 @@ class Swe2dDevice(object):
             # bisection boxes (ordering.flow_block_order) instead of 64 consecutive cells of the device numbering - a fifth to a
             # third fewer rim facets
             self.flow_set_order(ordering.flow_block_order(mesh))
-        tt = os.environ.get('THETIS_AMD_TRIPLE_TILE', '11,8')
+        tt = ordering.triple_tile_shape() if self.npc == 3 else None
         if (self.npc == 3 and isinstance(reorder, str) and self.n_owned == self.n_cells and getattr(mesh, 'structured', False)
-                and self.n_cells > 131072 and tt != '0'):
+                and self.n_cells > 131072 and tt is not None):
             # a mesh beyond the dataflow kernel: all three stages of a step in one launch (csrc/swe2d_fuse.h, swe_fuse123_kernel) on
             # two-ring tiles cut as patches of 11 x 8 quads - 176 triangles + rings of 38 + 42 = the 256 lanes - instead of as many
             # consecutive cells of the 16 x 6 numbering as fit (147 + 52 + 57, ragged: 1 M cells 110.7 -> 96.8 us per step, where the
             # fused pair takes 103.4; profiles/r06l_triple_tiles.txt).  THETIS_AMD_TRIPLE_TILE = "bx,by" | 0: A/B runs
-            bx, by = (int(v) for v in tt.split(','))
-            self.fused_set_triple_tiles(*ordering.triple_tile_order(mesh, bx, by))
+            self.fused_set_triple_tiles(*ordering.triple_tile_order(mesh, *tt))
         if self.npc == 4 and not getattr(mesh, 'affine', True):
             # a partition (LocalPartition.affine = the GLOBAL mesh's flag) whose own cells happen to be parallelograms takes the
             # general kernels like every other rank: ghost and owned copies of a cell then agree bit for bit

@@ -361,8 +361,8 @@ class DistributedSwe2d(object):
             self.dev.fused_pair_info()
             # ... and the two-ring tiles of a whole step in one launch (swe2d_solve_step_cells: pairs of steps of a cycle, see
             # _cycle_before_exchange): the 11 x 8-quad patches of the parent mesh, over owned and ghost cells alike
-            tt = os.environ.get('THETIS_AMD_TRIPLE_TILE', '11,8')
-            tiles = ordering.triple_tile_order(p, *(int(v) for v in tt.split(','))) if tt != '0' else None
+            tt = ordering.triple_tile_shape()
+            tiles = ordering.triple_tile_order(p, *tt) if tt is not None else None
             if tiles is not None:
                 self.dev.fused_set_triple_tiles(*tiles)
             self.dev.fused_step_info()

@@ -5,9 +5,12 @@ facet-neighbour gathers mostly hit lines it loaded itself and (ii) the contiguou
 XCD works on (swe_logical_block in csrc/swe2d_kernels.h) only shares a thin seam with the other XCDs' L2s.
 Firedrake gives the reference the same service by reordering DMPlex points (reverse Cuthill-McKee) [FD-assumed].
 """
+import os
+import warnings
+
 import numpy as np
 
-__all__ = ['hilbert_index', 'hilbert_cell_order', 'tile_cell_order', 'structured_tile_order', 'structured_subset_order', 'auto_cell_order', 'flow_block_order', 'fused_tile_order', 'triple_tile_order', 'bisection_block_order',
+__all__ = ['hilbert_index', 'hilbert_cell_order', 'tile_cell_order', 'structured_tile_order', 'structured_subset_order', 'auto_cell_order', 'flow_block_order', 'fused_tile_order', 'triple_tile_order', 'triple_tile_shape', 'bisection_block_order',
            'patch_row_order', 'first_touch_vertex_order']
 
 
@@ -223,6 +226,24 @@ def triple_tile_order(mesh, bx=11, by=8):
     pk = patch[order]
     starts = np.nonzero(np.concatenate(([True], pk[1:] != pk[:-1])))[0]
     return order, starts
+
+
+def triple_tile_shape(default=(11, 8)):
+    """The patch shape of ``triple_tile_order`` from THETIS_AMD_TRIPLE_TILE ("bx,by"; "0": no patches, ``None``; unset: ``default``).
+    A malformed value is reported with a warning and the default is taken (an A/B switch must not stop a run)."""
+    tt = os.environ.get('THETIS_AMD_TRIPLE_TILE')
+    if tt is None or tt.strip() == '':
+        return default
+    if tt.strip() == '0':
+        return None
+    try:
+        bx, by = (int(v) for v in tt.split(','))
+        if bx <= 0 or by <= 0:
+            raise ValueError('patch sides must be positive')
+        return bx, by
+    except ValueError as e:
+        warnings.warn('THETIS_AMD_TRIPLE_TILE={!r} is not "bx,by" or "0" ({}): using {},{}'.format(tt, e, *default))
+        return default
 
 
 def first_touch_vertex_order(cells):
