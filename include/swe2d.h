@@ -528,6 +528,46 @@ int  swe2d_probe_read(swe2d_handle *h, int32_t probe_id, double *out, int32_t *n
 int  swe2d_probe_eval(swe2d_handle *h, int32_t probe_id, double *out);
 int  swe2d_probe_destroy(swe2d_handle *h, int32_t probe_id);
 
+/* ---- Tidal turbine farms (thetis/turbines.py:17-171, TurbineDragTerm shallowwater_eq.py:765-791).
+ * A farm is a turbine type (constant or tabulated thrust), a nodal turbine density d(x) >= 0 that is zero outside the farm's
+ * cells, and per-farm constants.  While a handle has farms, the momentum equation carries
+ *     - c_t(|u|, H) d |u| u / H,   c_t = (C_T A_T + C_support A_support) / (2 alpha^2),
+ *     alpha = upwind_correction ? (1 + sqrt(1 - (C_T A_T + C_support A_support)/(D_proj H)))/2 : 1,
+ * integrated with the rule of the quadratic bottom drag, and every stepping path that does not evaluate it declines the handle:
+ * the steps run as stage launches (swe2d_fused_pair_info / _triple_info / _step_info report 0, swe2d_flow_supported 0).
+ * The thrust table: C_T = 0 below speeds[0], linear between entries, 0 from speeds[n_table - 1] on. */
+#define SWE2D_MAX_FARMS 8
+#define SWE2D_MAX_THRUST_TABLE 16
+typedef struct {
+    double  thrust_area_const;       /* C_T A_T of a constant-thrust turbine (n_table == 0) */
+    double  support_area;            /* C_support A_support */
+    double  rotor_area;              /* A_T = pi D^2 / 4 */
+    double  projected_diameter;      /* D_proj (upwind correction) */
+    double  power_const;             /* C_P of a constant-thrust turbine */
+    double  rho0;                    /* physical_constants['rho0'] (power only) */
+    int32_t upwind_correction;       /* 0 / 1 */
+    int32_t n_table;                 /* 0: constant thrust; else 2 .. SWE2D_MAX_THRUST_TABLE entries, speeds strictly increasing */
+    double  speeds[SWE2D_MAX_THRUST_TABLE];
+    double  thrust[SWE2D_MAX_THRUST_TABLE];     /* C_T at speeds[] */
+    double  power[SWE2D_MAX_THRUST_TABLE];      /* C_P at speeds[] */
+} swe2d_turbine_params;
+/* Sets (or replaces) farm `farm` in 0 .. SWE2D_MAX_FARMS-1.  density_nodal: [n_cells][nodes_per_cell], >= 0, zero in every cell
+ * outside the farm; cells with a non-zero density form the farm's cell list (what the power kernel visits). */
+int  swe2d_turbine_farm_set(swe2d_handle *h, int32_t farm, const swe2d_turbine_params *p, const double *density_nodal);
+int  swe2d_turbine_farm_clear(swe2d_handle *h, int32_t farm);
+/* Power of every farm slot (0 for an empty slot), int 0.5 rho0 A_T C_P(u3^(1/3)) u3 d dx with u3 = |u|^3 / alpha^3 and alpha formed
+ * with the static bathymetry (TurbineFunctionalCallback, turbines.py:85-93, 233, 252), over the OWNED cells, of the state in buffer
+ * A.  Synchronous.  _limbs: the same as order-independent limb sums [SWE2D_MAX_FARMS][6] (swe2d_diagnostics_limbs): partitions add
+ * them as integers and round once with swe2d_sum_limbs_to_double - the doubles of one handle on the whole mesh. */
+int  swe2d_turbine_power(swe2d_handle *h, double out[SWE2D_MAX_FARMS]);
+int  swe2d_turbine_power_limbs(swe2d_handle *h, int64_t limbs[SWE2D_MAX_FARMS*6]);
+/* Power rows on the device, as the probe rows: _reserve sets the capacity (and empties the store), _append enqueues ONE launch that
+ * writes the limb sums of the current state into the next row (no synchronisation), _read synchronises, returns the rows appended
+ * since the last read as doubles [n_rows][SWE2D_MAX_FARMS] and empties the store.  Refused inside a stream capture. */
+int  swe2d_turbine_rows_reserve(swe2d_handle *h, int32_t capacity);
+int  swe2d_turbine_rows_append(swe2d_handle *h);
+int  swe2d_turbine_rows_read(swe2d_handle *h, double *out, int32_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,9 @@ from .expr import *  # noqa: F401,F403  (SpatialCoordinate, conditional, as_vect
 from .function import Function, FunctionSpace, get_functionspace  # noqa: F401
 from .mesh import Mesh2d, PeriodicRectangleMesh, RectangleMesh, SquareMesh, UnitSquareMesh  # noqa: F401
 from .meshio import read_gmsh, write_gmsh  # noqa: F401
-from .options import Constant, ModelOptions2d  # noqa: F401
+from .options import (Constant, ModelOptions2d, TidalTurbineFarmOptions, DiscreteTidalTurbineFarmOptions,  # noqa: F401
+                      ConstantTidalTurbineOptions, TabulatedTidalTurbineOptions, TidalTurbineOptions)
+from . import turbines  # noqa: F401
 from .shallowwater_eq import g_grav, physical_constants, rho_0  # noqa: F401
 
 

@@ -26,6 +26,7 @@ ABI_VERSION = 12         # include/swe2d.h SWE2D_ABI_VERSION
  OPT_FLOW_POLL, OPT_FLOW_CAPACITY, OPT_FLOW_TIMEOUT_MS, OPT_P2P_TIMEOUT_MS, OPT_P2P_ZONE, OPT_ROCTX) = range(15)
 OPT_COUNT = 15
 SNAPSHOT_SLOTS = 2
+MAX_FARMS, MAX_THRUST_TABLE = 8, 16   # include/swe2d.h SWE2D_MAX_FARMS, SWE2D_MAX_THRUST_TABLE
 PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
@@ -81,6 +82,15 @@ class Swe2dParams(ctypes.Structure):
     _fields_ = [('g_grav', ctypes.c_double), ('dt', ctypes.c_double),
                 ('use_nonlinear_equations', ctypes.c_int32), ('use_lax_friedrichs_velocity', ctypes.c_int32),
                 ('lax_friedrichs_velocity_scaling_factor', ctypes.c_double), ('device_id', ctypes.c_int32)]
+
+
+class TurbineParams(ctypes.Structure):
+    """include/swe2d.h swe2d_turbine_params"""
+    _fields_ = [('thrust_area_const', ctypes.c_double), ('support_area', ctypes.c_double), ('rotor_area', ctypes.c_double),
+                ('projected_diameter', ctypes.c_double), ('power_const', ctypes.c_double), ('rho0', ctypes.c_double),
+                ('upwind_correction', ctypes.c_int32), ('n_table', ctypes.c_int32),
+                ('speeds', ctypes.c_double*MAX_THRUST_TABLE), ('thrust', ctypes.c_double*MAX_THRUST_TABLE),
+                ('power', ctypes.c_double*MAX_THRUST_TABLE)]
 
 
 # every symbol include/swe2d.h declares: name -> (restype, argtypes)
@@ -190,6 +200,13 @@ SYMBOLS = {
     'swe2d_probe_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip]),
     'swe2d_probe_eval': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
     'swe2d_probe_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_turbine_farm_set': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.POINTER(TurbineParams), _dp]),
+    'swe2d_turbine_farm_clear': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_turbine_power': (ctypes.c_int, [_H, _dp]),
+    'swe2d_turbine_power_limbs': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_turbine_rows_reserve': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_turbine_rows_append': (ctypes.c_int, [_H]),
+    'swe2d_turbine_rows_read': (ctypes.c_int, [_H, _dp, _ip]),
 }
 
 _lib = None

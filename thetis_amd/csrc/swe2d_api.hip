@@ -83,6 +83,7 @@ void fill_stage_args(Handle *h, SweStageArgs &a, int in, int u0, int out, double
     a.nu_v = h->nu_v; a.nu_const = h->nu_const;
     a.visc_sipg = 3.0*h->sipg_factor;
     a.visc_grad_div = h->visc_grad_div; a.visc_grad_depth = h->visc_grad_depth;
+    a.farms = h->n_farms > 0 ? h->farm_table : nullptr;
 }
 
 // Launch one stage on cells [c0, c1).  in/out/u0 are state buffer indices.
@@ -536,6 +537,7 @@ void swe2d_destroy(swe2d_handle *hh)
     (void)hipSetDevice(h->device);
     if (h->my_stream) (void)hipStreamSynchronize(h->my_stream);
     probe_free_all(h);
+    farm_free_all(h);
     for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
     for (auto &t : h->tracers) {

@@ -123,6 +123,7 @@ int flow_build(Handle *h, const int32_t *order)
 bool flow_kernel_covers(const Handle *h)
 {
     if (h->wd && (!h->par.use_nonlinear_equations || !opt_on(h, SWE2D_OPT_FLOW_WD))) return false;
+    if (h->n_farms > 0) return false;                        // tidal turbine farms: stage launches (swe_source_terms<true>)
     return h->npc == 3 && !h->visc && h->idx4 && h->flow_flag && h->flow_ex && h->opt[SWE2D_OPT_BND_INLINE] != 0;
 }
 

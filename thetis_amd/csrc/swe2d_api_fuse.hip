@@ -29,6 +29,7 @@ static bool fuse_applies(const Handle *h)                      // what every fus
 {
     if (h->opt[SWE2D_OPT_FUSED_STAGES] == 0) return false;
     if (h->opt[SWE2D_OPT_BND_INLINE] == 0) return false;     // the epilogue variant was asked for
+    if (h->n_farms > 0) return false;                        // tidal turbine farms: the stage kernels carry the term, the tiles do not
     return !h->wd && !h->visc && !h->h_nbr.empty();
 }
 

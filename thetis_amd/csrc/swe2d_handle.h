@@ -22,6 +22,7 @@
 #include <mutex>
 
 static_assert(SWE2D_MAX_MARKERS == SWE_MAX_MARKERS, "marker table size mismatch");
+static_assert(SWE2D_MAX_FARMS == SWE_MAX_FARMS && SWE2D_MAX_THRUST_TABLE == SWE_MAX_THRUST_TABLE, "turbine farm table size mismatch");
 
 #ifdef SWE_RANGE_CHECK
 // Range-checked build (swe2d_kernels.h): every device allocation of this library is recorded with its requested size;
@@ -245,6 +246,20 @@ struct Handle {
         std::vector<int> fields;                        // SWE2D_PROBE_UV / SWE2D_PROBE_ELEV / tracer id
     };
     std::vector<Probe> probes;
+    // tidal turbine farms (swe2d_turbine.hip): slot = farm id
+    struct Farm {
+        bool live = false;
+        swe2d_turbine_params par{};
+        double *density = nullptr;                      // npc nodal planes, zero outside the farm's cells
+        int *cells = nullptr;                           // owned cells with a non-zero density
+        int n_list = 0;
+    };
+    Farm farms[SWE2D_MAX_FARMS];
+    int n_farms = 0;                                    // live slots
+    SweFarmTable *farm_table = nullptr;                 // the device's copy of the farms' constants (SweStageArgs::farms)
+    int farm_blocks = 0;                                // blocks of a power launch
+    unsigned long long *farm_rows = nullptr;            // [farm_rows_cap + 1][SWE_FARM_ROW] limb sums; the last row is swe2d_turbine_power's
+    int farm_rows_cap = 0, farm_rows_n = 0;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -310,6 +325,7 @@ inline RoctxRange::RoctxRange(const Handle *h, const char *name)
 inline bool has_sources(const Handle *h)
 {
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) return true;
+    if (h->n_farms > 0) return true;
     return h->scalar[SWE2D_SCALAR_LINEAR_DRAG] >= 0 || h->scalar[SWE2D_SCALAR_QUADRATIC_DRAG] >= 0
            || h->scalar[SWE2D_SCALAR_MANNING_DRAG] >= 0 || h->scalar[SWE2D_SCALAR_NIKURADSE] >= 0;
 }
@@ -358,6 +374,8 @@ int flow_check(Handle *h);
 size_t p2p_channel_offset(const int *width, int c, int n_recv);
 // ---- point probes (swe2d_probe.hip): frees every probe set of the handle (swe2d_destroy)
 void probe_free_all(Handle *h);
+// ---- tidal turbine farms (swe2d_turbine.hip): frees every farm and the power rows (swe2d_destroy)
+void farm_free_all(Handle *h);
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -51,6 +51,30 @@ struct SweBcTable {
     double drag[SWE_MAX_MARKERS];     // boundary drag C_D ('drag' key, BoundaryDragTerm), < 0: none
 };
 
+// Tidal turbine farms (thetis/turbines.py:36-58, :109-141; TurbineDragTerm shallowwater_eq.py:783-791): the per-farm constants live in
+// ONE table in device memory that every lane reads at uniform addresses (scalar loads where the compiler can prove it, else
+// broadcast vector loads of a few cache lines) - a thrust table does not fit kernel arguments eight times over.
+#define SWE_MAX_FARMS 8
+#define SWE_MAX_THRUST_TABLE 16
+struct SweFarm {
+    double thrust_area_const;         // C_T A_T (constant thrust)
+    double support_area;              // C_support A_support
+    double half_rho_area;             // 0.5 rho0 A_T (power)
+    double rdproj;                    // 1 / projected diameter
+    double power_const;               // C_P (constant thrust)
+    double rotor_area;                // A_T
+    int upwind, n_table;              // n_table == 0: constant thrust
+    double speeds[SWE_MAX_THRUST_TABLE], thrust[SWE_MAX_THRUST_TABLE], power[SWE_MAX_THRUST_TABLE];
+    double rdx[SWE_MAX_THRUST_TABLE]; // 1 / (speeds[j + 1] - speeds[j])
+    const double *density;            // k nodal planes of `stride` doubles, zero outside the farm's cells
+    const int *cells;                 // the owned cells with a non-zero density (power kernel)
+    int n_list, block0;               // length of `cells`; first block of the power launch that works on this farm
+};
+struct SweFarmTable {
+    int live[SWE_MAX_FARMS];
+    SweFarm f[SWE_MAX_FARMS];
+};
+
 struct SweStageArgs {
     const double *uin;     // 9 planes, state entering the stage
     const double *u0;      // 9 planes, stage_sol[0]
@@ -98,6 +122,7 @@ struct SweStageArgs {
     const double *quad_f;     // quadratic C_D, Manning mu or Nikuradse k_s, according to quad_f_kind
     int quad_f_kind;          // 0 none, 1 quadratic, 2 Manning, 3 Nikuradse
     SweBcTable bc;
+    const SweFarmTable *farms;   // tidal turbine farms or null (kept last: the offsets of everything above are those of a build without farms)
 };
 
 // 2-point Gauss-Legendre on [0,1] (facet rule of degree 3, shallowwater_eq.py:225-230 [FD-assumed])
@@ -596,8 +621,116 @@ __device__ __forceinline__ void swe_st_chk(swe_rsrc_t r, unsigned voff, unsigned
 #define swe_st(r, v, s, x) swe_st_chk(r, v, s, x, __LINE__)
 #endif
 
+// ---- tidal turbine farms ---------------------------------------------------------------------------------------------------
+// y(s) of a farm's table: 0 below x[0], linear between entries, 0 from x[n - 1] on (turbines.py:109-141).  The table is uniform
+// across the wave: a loop of uniform trip count whose body is compares and selects, no divergent search.
+__device__ __forceinline__ double swe_farm_table(const double *x, const double *y, const double *rdx, int n, double s)
+{
+#pragma clang fp contract(off)
+    double r = 0.0;
+    for (int j = 0; j + 1 < n; j++) {
+        const double x0 = x[j], x1 = x[j + 1];
+        const double v = ((x1 - s)*y[j] + (s - x0)*y[j + 1])*rdx[j];
+        r = (s >= x0 && s < x1) ? v : r;
+    }
+    return r;
+}
+// C_T A_T + C_support A_support at speed umag (turbines.py:36-42)
+__device__ __forceinline__ double swe_farm_thrust_area(const SweFarm &F, double umag)
+{
+#pragma clang fp contract(off)
+    const double ta = F.n_table > 0 ? swe_farm_table(F.speeds, F.thrust, F.rdx, F.n_table, umag)*F.rotor_area : F.thrust_area_const;
+    return ta + F.support_area;
+}
+// ratio of the velocity at the turbine to the upstream velocity (turbines.py:44-49); a negative radicand gives NaN, as there
+__device__ __forceinline__ double swe_farm_alpha(const SweFarm &F, double fric, double rdepth)
+{
+#pragma clang fp contract(off)
+    return 0.5*(1.0 + swe_sqrt(1.0 - fric*F.rdproj*rdepth));
+}
+// c_t d |u| / H at a point (turbines.py:51-58, shallowwater_eq.py:788-790; no norm_smoother): the factor of -u in the momentum equation
+__device__ __forceinline__ double swe_farm_drag_pt(const SweFarm &F, double uq, double vq, double Hq, double dq)
+{
+#pragma clang fp contract(off)
+    const double umag = swe_sqrt(fma(uq, uq, vq*vq));
+    const double rH = swe_rcp(Hq);
+    const double fric = swe_farm_thrust_area(F, umag);
+    double c = 0.5*fric;
+    if (F.upwind) {                                       // uniform
+        const double al = swe_farm_alpha(F, fric, rH);
+        c = c*swe_rcp(al*al);
+    }
+    return c*dq*umag*rH;
+}
+// TurbineDragTerm of a triangle, by the orbits of the 6-point rule like the quadratic drag of swe_source_terms
+__device__ __forceinline__ void swe_farm_terms(const SweStageArgs &p, int k, size_t S, double A, const double u[3], const double v[3],
+                                               const double H[3], double bu[3], double bv[3])
+{
+#pragma clang fp contract(off)
+    const double a1 = 0.445948490915965, b1 = 0.108103018168070, w1 = 0.223381589678011;
+    const double a2 = 0.091576213509771, b2 = 0.816847572980459, w2 = 0.109951743655322;
+    const unsigned S8 = (unsigned)S*8u, k8 = (unsigned)k*8u;
+    const double us = u[0] + u[1] + u[2], vs = v[0] + v[1] + v[2], Hs = H[0] + H[1] + H[2];
+    const SweFarmTable *ft = p.farms;
+#pragma unroll 1
+    for (int m = 0; m < SWE_MAX_FARMS; m++) {
+        if (!ft->live[m]) continue;                          // uniform
+        const SweFarm &F = ft->f[m];
+        double d[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) d[i] = swe_ld(swe_rsrc(F.density), k8, i*S8);
+        if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) continue;      // a cell outside the farm: its lanes sit this farm out
+        const double ds = d[0] + d[1] + d[2];
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const double aa = o ? a2 : a1, dd = o ? b2 - a2 : b1 - a1, wA = (o ? w2 : w1)*A;
+            const double au = aa*us, av = aa*vs, aH = aa*Hs, ad = aa*ds;
+            double su[3], sv[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const double uq = fma(dd, u[i], au), vq = fma(dd, v[i], av), Hq = fma(dd, H[i], aH), dq = fma(dd, d[i], ad);
+                const double s = wA*swe_farm_drag_pt(F, uq, vq, Hq, dq);
+                su[i] = s*uq;
+                sv[i] = s*vq;
+            }
+            const double aSu = aa*(su[0] + su[1] + su[2]), aSv = aa*(sv[0] + sv[1] + sv[2]);
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                bu[i] -= fma(dd, su[i], aSu);
+                bv[i] -= fma(dd, sv[i], aSv);
+            }
+        }
+    }
+}
+// ... and of a quadrilateral at one point of its rule (phi: the four basis functions there): the sum over the farms of c_t d |u| / H
+__device__ __forceinline__ double swe_farm_drag_quad(const SweStageArgs &p, unsigned k8, unsigned S8, const double phi[4], double uq,
+                                                     double vq, double Hq)
+{
+#pragma clang fp contract(off)
+    const SweFarmTable *ft = p.farms;
+    double drag = 0.0;
+#pragma unroll 1
+    for (int m = 0; m < SWE_MAX_FARMS; m++) {
+        if (!ft->live[m]) continue;                          // uniform
+        const SweFarm &F = ft->f[m];
+        double dq = 0.0, dabs = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const double di = swe_ld(swe_rsrc(F.density), k8, i*S8);
+            dq = fma(phi[i], di, dq);
+            dabs += fabs(di);
+        }
+        if (dabs == 0.0) continue;
+        drag += swe_farm_drag_pt(F, uq, vq, Hq, dq);
+    }
+    return drag;
+}
+
 // Optional cell-local terms (SRC kernel variant): Coriolis, linear / quadratic / Manning drag, atmospheric pressure
 // gradient, momentum and volume sources.  b-vectors are the assembled integrals (before the mass inverse).
+// FARMS: the instance also carries the tidal turbine farms (the stage kernels; the fused and the dataflow kernels, which have no
+// registers to spare, do not - handles with farms never reach them, see fuse_applies / flow_kernel_covers).
+template <bool FARMS = false>
 __device__ __forceinline__ void swe_source_terms(const SweStageArgs &p, int k, size_t S, double twoA, const double u[3],
                                                  const double v[3], const double H[3], const double gxs[3],
                                                  const double gys[3], double bu[3], double bv[3], double be[3])
@@ -787,6 +920,9 @@ __device__ __forceinline__ void swe_source_terms(const SweStageArgs &p, int k, s
         const double ss = sv_[0] + sv_[1] + sv_[2];
 #pragma unroll
         for (int i = 0; i < 3; i++) be[i] = fma(A12, ss + sv_[i], be[i]);
+    }
+    if constexpr (FARMS) {
+        if (p.farms) swe_farm_terms(p, k, S, A, u, v, H, bu, bv);
     }
 }
 
@@ -1239,7 +1375,7 @@ __global__ __launch_bounds__(SWE_BLOCK, SWE_MIN_WAVES) void swe_stage_kernel(con
 
     // optional cell-local terms AFTER the facet loop: the 18 neighbour traces are dead by now, which keeps the SRC variants
     // at 146 (162 with wetting-drying) VGPRs = 3 waves/SIMD instead of 188 (194) = 2
-    if (SRC) swe_source_terms(p, k, S, twoA, u, v, H, gxs, gys, bu, bv, be);
+    if (SRC) swe_source_terms<true>(p, k, S, twoA, u, v, H, gxs, gys, bu, bv, be);
     if (VISC) swe_visc_interior(p, k, S8, gu, gv, nb, vid, u, v, una, unb, vna, vnb, px, py, nx, ny, Lf, rLf, twoA, H, bu, bv);
 
     // ---- mass inverse (M^-1 b)_i = 3/A (4 b_i - sum b), times dt, and the Shu-Osher combine
@@ -2500,6 +2636,10 @@ __device__ __forceinline__ void swe_quad_stage_cell(const SweStageArgs &p, int k
 #pragma unroll
                 for (int i = 0; i < 4; i++) drag += phi[i]*swe_ld(swe_rsrc(p.lin_drag_f), k8, i*S8);
             } else if (p.linear_drag >= 0.0) drag += p.linear_drag;
+            // tidal turbine farms: stage launches only (the tiles of the fused stage pair decline handles with farms)
+            if constexpr (!TILE) {
+                if (p.farms) drag += swe_farm_drag_quad(p, k8, S8, phi, uq, vq, Hq);
+            }
             const double cu = Aq*(corq*vq - drag*uq + sx) - gpx*(1.0/1000.0);
             const double cv_ = Aq*(-corq*uq - drag*vq + sy) - gpy*(1.0/1000.0);
             const double ce = Aq*sv;

@@ -13,3 +13,4 @@
 #include "swe2d_k_flow_wd.hip"
 #include "swe2d_k_tracer.hip"
 #include "swe2d_probe.hip"
+#include "swe2d_turbine.hip"

@@ -592,10 +592,14 @@ class Swe2dDevice(object):
 
     def probe_append(self, pid):
         """one row of the current state, enqueued (no synchronisation)"""
+        if pid == self.TURBINE_ROWS:
+            return self.turbine_rows_append()
         self._ck(self.lib.swe2d_probe_append(self.h, int(pid)))
 
     def probe_read(self, pid):
         """the rows appended since the last read, (rows, points, components); the set is empty afterwards"""
+        if pid == self.TURBINE_ROWS:
+            return self.turbine_rows_read()
         m, w, c = self.probe_shape(pid)
         out = np.empty((max(c, 1), m, w))
         n = ctypes.c_int32()
@@ -611,6 +615,44 @@ class Swe2dDevice(object):
 
     def probe_destroy(self, pid):
         self._ck(self.lib.swe2d_probe_destroy(self.h, int(pid)))
+
+    # -- tidal turbine farms: csrc/swe2d_turbine.hip
+    TURBINE_ROWS = -100       # the "probe id" of the power rows: the batched time loop appends and reads them like a probe set's
+
+    def turbine_farm_set(self, farm, params, density_nodal):
+        """farm slot ``farm``: ``params`` (_lib.TurbineParams) and the nodal density (N, k), zero outside the farm's cells"""
+        d = self._nodal_in(density_nodal)
+        self._ck(self.lib.swe2d_turbine_farm_set(self.h, int(farm), ctypes.byref(params), _ptr(d)))
+
+    def turbine_farm_clear(self, farm):
+        self._ck(self.lib.swe2d_turbine_farm_clear(self.h, int(farm)))
+
+    def turbine_power(self):
+        """power of every farm slot (MAX_FARMS,), synchronously"""
+        out = np.zeros(_lib.MAX_FARMS)
+        self._ck(self.lib.swe2d_turbine_power(self.h, _ptr(out)))
+        return out
+
+    def turbine_power_limbs(self):
+        """... as order-independent limb sums (MAX_FARMS, SUM_LIMBS) of the owned cells"""
+        limbs = np.zeros(_lib.MAX_FARMS*_lib.SUM_LIMBS, dtype=np.int64)
+        self._ck(self.lib.swe2d_turbine_power_limbs(self.h, limbs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return limbs.reshape(_lib.MAX_FARMS, _lib.SUM_LIMBS)
+
+    def turbine_rows_reserve(self, capacity):
+        self._turbine_rows_cap = int(capacity)
+        self._ck(self.lib.swe2d_turbine_rows_reserve(self.h, int(capacity)))
+
+    def turbine_rows_append(self):
+        """one power row of the current state, enqueued (no synchronisation)"""
+        self._ck(self.lib.swe2d_turbine_rows_append(self.h))
+
+    def turbine_rows_read(self):
+        """the rows appended since the last read, (rows, MAX_FARMS); the store is empty afterwards"""
+        out = np.empty((max(getattr(self, '_turbine_rows_cap', 0), 1), _lib.MAX_FARMS))
+        n = ctypes.c_int32()
+        self._ck(self.lib.swe2d_turbine_rows_read(self.h, _ptr(out), ctypes.byref(n)))
+        return out[:n.value].copy()
 
     # -- tracers + limiter
     def _nodal_in(self, a):

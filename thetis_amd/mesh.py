@@ -32,12 +32,15 @@ def _signed_area2(p):
 class Mesh2d(object):
     """2D mesh of triangles or (convex) quadrilaterals with facet-neighbour connectivity."""
 
-    def __init__(self, vertex_xy, cells, topo_vertex=None, marker_fn=None, name='mesh2d'):
+    def __init__(self, vertex_xy, cells, topo_vertex=None, marker_fn=None, name='mesh2d', cell_marker_fn=None,
+                 cell_markers=None):
         """
         :arg vertex_xy: (V, 2) vertex coordinates
         :arg cells: (N, 3) vertex ids (any orientation; made counter-clockwise here)
         :kwarg topo_vertex: (V,) canonical vertex id used for *topology* (periodic identification)
         :kwarg marker_fn: callable(xm, ym) -> int marker (>0) for exterior facet mid-points
+        :kwarg cell_marker_fn: callable(xc, yc) -> int subdomain id of the cells, evaluated at their centroids
+        :kwarg cell_markers: (N,) subdomain ids given directly (a mesh file's cell tags); default 0 everywhere
         """
         self.name = name
         self.vertex_xy = np.ascontiguousarray(vertex_xy, dtype=np.float64)
@@ -72,6 +75,16 @@ class Mesh2d(object):
                             else np.asarray(topo_vertex, dtype=np.int64))
         self._build_connectivity(marker_fn)
         self.boundary_len = self._boundary_length()
+        # subdomain id per cell (``dx(id)`` of the reference: where a tidal turbine farm acts)
+        if cell_markers is not None:
+            cm = np.asarray(cell_markers)
+            assert cm.shape == (self.num_cells,), 'cell_markers must hold one id per cell'
+        elif cell_marker_fn is not None:
+            cen = self.cell_xy().mean(axis=1)
+            cm = np.broadcast_to(np.asarray(cell_marker_fn(cen[:, 0], cen[:, 1])), (self.num_cells,))
+        else:
+            cm = np.zeros(self.num_cells)
+        self.cell_markers = np.ascontiguousarray(cm, dtype=np.int32)
 
     # ------------------------------------------------------------------ topology
     def _build_connectivity(self, marker_fn):
@@ -171,6 +184,7 @@ class Mesh2d(object):
         new.cell_nbr = np.ascontiguousarray(nb.astype(np.int32))
         new.cell_nbr_facet = np.ascontiguousarray(self.cell_nbr_facet[perm])
         new.boundary_len = dict(self.boundary_len)
+        new.cell_markers = np.ascontiguousarray(self.cell_markers[perm])
         for k in ('nx', 'ny', 'lx', 'ly'):
             if hasattr(self, k):
                 setattr(new, k, getattr(self, k))
@@ -220,20 +234,22 @@ def _rect_marker_fn(lx, ly, periodic_x=False, periodic_y=False):
     return fn
 
 
-def RectangleMesh(nx, ny, lx, ly, quadrilateral=False, diagonal='left', name='mesh2d'):
-    """``RectangleMesh(nx, ny, Lx, Ly)``: 2*nx*ny triangles or nx*ny quadrilaterals, markers 1..4 [FD-assumed, A.8]."""
+def RectangleMesh(nx, ny, lx, ly, quadrilateral=False, diagonal='left', name='mesh2d', cell_marker_fn=None):
+    """``RectangleMesh(nx, ny, Lx, Ly)``: 2*nx*ny triangles or nx*ny quadrilaterals, markers 1..4 [FD-assumed, A.8].
+    ``cell_marker_fn(xc, yc) -> int``: subdomain ids of the cells (by centroid), next to the boundary markers."""
     xs = np.linspace(0.0, lx, nx + 1)
     ys = np.linspace(0.0, ly, ny + 1)
     xx, yy = np.meshgrid(xs, ys, indexing='ij')
     vertex_xy = np.stack([xx.ravel(), yy.ravel()], axis=1)
     cells = _grid_quads(nx, ny) if quadrilateral else _grid_cells(nx, ny, diagonal)
-    mesh = Mesh2d(vertex_xy, cells, marker_fn=_rect_marker_fn(lx, ly), name=name)
+    mesh = Mesh2d(vertex_xy, cells, marker_fn=_rect_marker_fn(lx, ly), name=name, cell_marker_fn=cell_marker_fn)
     mesh.nx, mesh.ny, mesh.lx, mesh.ly = nx, ny, float(lx), float(ly)
     mesh.structured = True              # cell = 2*(j*nx + i) + t: lets the device pick a tiled numbering
     return mesh
 
 
-def PeriodicRectangleMesh(nx, ny, lx, ly, direction='x', quadrilateral=False, diagonal='left', name='mesh2d'):
+def PeriodicRectangleMesh(nx, ny, lx, ly, direction='x', quadrilateral=False, diagonal='left', name='mesh2d',
+                          cell_marker_fn=None):
     """Rectangle periodic in ``direction`` ('x', 'y' or 'both'); geometry stays unwrapped."""
     xs = np.linspace(0.0, lx, nx + 1)
     ys = np.linspace(0.0, ly, ny + 1)
@@ -246,7 +262,8 @@ def PeriodicRectangleMesh(nx, ny, lx, ly, direction='x', quadrilateral=False, di
         jj = jj % ny
     topo = (ii*(ny + 1) + jj).ravel()
     cells = _grid_quads(nx, ny) if quadrilateral else _grid_cells(nx, ny, diagonal)
-    mesh = Mesh2d(vertex_xy, cells, topo_vertex=topo, marker_fn=_rect_marker_fn(lx, ly), name=name)
+    mesh = Mesh2d(vertex_xy, cells, topo_vertex=topo, marker_fn=_rect_marker_fn(lx, ly), name=name,
+                  cell_marker_fn=cell_marker_fn)
     mesh.nx, mesh.ny, mesh.lx, mesh.ly = nx, ny, float(lx), float(ly)
     mesh.structured = True
     return mesh

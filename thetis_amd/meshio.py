@@ -3,7 +3,8 @@ Mesh files: Gmsh MSH 2.2 ASCII, the format of every ``.msh`` the reference ships
 examples/*/mesh*.msh; Firedrake's ``Mesh('file.msh')`` reads them through DMPlex [FD-assumed]).
 
 Triangles (element type 2) and quadrilaterals (type 3) become cells; line elements (type 1) carry the physical tags that
-become boundary markers (``ds(tag)`` in the reference).  Exterior facets without a line element get ``default_marker``.
+become boundary markers (``ds(tag)`` in the reference); the first tag of a triangle / quadrilateral is the cell's subdomain id
+(``dx(tag)``, ``Mesh2d.cell_markers``; 0 without tags).  Exterior facets without a line element get ``default_marker``.
 """
 import numpy as np
 
@@ -32,7 +33,7 @@ def read_gmsh(path, default_marker=None, name=None):
     id2idx[node_ids] = np.arange(n_nodes)
     i = pos['$Elements'] + 1
     n_el = int(lines[i])
-    cells, edges, edge_tags = [], [], []
+    cells, cell_tags, edges, edge_tags = [], [], [], []
     cell_type = None
     for l in lines[i + 1:i + 1 + n_el]:
         t = l.split()
@@ -45,6 +46,7 @@ def read_gmsh(path, default_marker=None, name=None):
                 raise NotImplementedError('{:}: mixed triangle/quadrilateral meshes are not supported'.format(path))
             cell_type = etype
             cells.append(nodes)
+            cell_tags.append(int(t[3]) if ntags > 0 else 0)       # first tag = physical entity: the subdomain id
         elif etype == 1:
             edges.append(nodes)
             edge_tags.append(int(t[3]) if ntags > 0 else 0)       # first tag = physical entity
@@ -58,7 +60,7 @@ def read_gmsh(path, default_marker=None, name=None):
     for (a, b), tag in zip(edges, edge_tags):
         a, b = remap[id2idx[a]], remap[id2idx[b]]
         tag_of[(min(a, b), max(a, b))] = tag
-    mesh = Mesh2d(xy[used], remap[cells], name=name or path)
+    mesh = Mesh2d(xy[used], remap[cells], name=name or path, cell_markers=cell_tags)
     # exterior facet markers from the line elements
     k = mesh.nodes_per_cell
     c, f = np.nonzero(mesh.cell_nbr < 0)
@@ -90,7 +92,10 @@ def write_gmsh(mesh, path):
             out.write('{:d} 1 2 {:d} {:d} {:d} {:d}\n'.format(e, tag, tag, a, b))
             e += 1
         etype = 2 if k == 3 else 3
-        for cell in mesh.cells:
-            out.write('{:d} {:d} 2 1 1 '.format(e, etype) + ' '.join(str(v + 1) for v in cell) + '\n')
+        tags = getattr(mesh, 'cell_markers', None)
+        if tags is None or not np.any(tags):
+            tags = np.ones(mesh.num_cells, dtype=np.int64)          # a mesh without subdomains: one surface, tag 1
+        for cell, tag in zip(mesh.cells, tags):
+            out.write('{:d} {:d} 2 {:d} {:d} '.format(e, etype, int(tag), int(tag)) + ' '.join(str(v + 1) for v in cell) + '\n')
             e += 1
         out.write('$EndElements\n')

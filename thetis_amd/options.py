@@ -11,7 +11,8 @@ is a small plain-Python restatement of the *behaviour*: typed/validated attribut
 from collections import OrderedDict
 
 __all__ = ['ModelOptions2d', 'ExplicitSWETimeStepperOptions2d', 'ExplicitTracerTimeStepperOptions2d',
-           'TimeStepperOptions', 'Constant']
+           'TimeStepperOptions', 'Constant', 'TidalTurbineOptions', 'ConstantTidalTurbineOptions',
+           'TabulatedTidalTurbineOptions', 'TidalTurbineFarmOptions', 'DiscreteTidalTurbineFarmOptions']
 
 
 class Constant(object):
@@ -59,6 +60,24 @@ def _positive_float(name, v):
 
 def _positive_float_or_none(name, v):
     return None if v is None else _positive_float(name, v)
+
+
+def _nonneg_float(name, v):
+    v = float(v)
+    assert v >= 0.0, "The '{:}' trait expected a non-negative float, not {:}".format(name, v)
+    return v
+
+
+def _float(name, v):
+    return float(v)
+
+
+def _float_list(name, v):
+    return [float(x) for x in v]
+
+
+def _float_list_or_none(name, v):
+    return None if v is None else _float_list(name, v)
 
 
 def _nonneg_int(name, v):
@@ -225,6 +244,74 @@ class TracerFieldOptions(object):
         self.use_conservative_form = False
 
 
+# ---- tidal turbines (options.py:460-531) ---------------------------------------------------------------------------
+class TidalTurbineOptions(FrozenOptions):
+    """Tidal turbine parameters (options.py:460-479)"""
+    name = 'Tidal turbine options'
+    _spec = OrderedDict([
+        ('diameter', (18.0, _positive_float)),
+        ('projected_diameter', (None, _positive_float_or_none)),       # defaults to diameter where it is used
+        ('C_support', (0.0, _nonneg_float)),
+        ('A_support', (0.0, _nonneg_float)),
+        ('apply_shear_profile', (False, _bool)),
+        ('shear_alpha', (7.0, _float)),
+        ('shear_beta', (0.4, _float)),
+        ('rel_hub_height', (None, _positive_float_or_none)),
+        ('structure_type', ('bottom-fixed', _enum('bottom-fixed', 'floating'))),
+    ])
+
+
+class ConstantTidalTurbineOptions(TidalTurbineOptions):
+    """Options for tidal turbine with constant thrust (options.py:482-490)"""
+    name = 'Constant tidal turbine options'
+    _spec = OrderedDict([
+        ('thrust_coefficient', (0.8, _positive_float)),
+        ('power_coefficient', (None, _positive_float_or_none)),        # None: 0.5 C_T (1 + sqrt(1 - C_T)), turbines.py:100
+    ])
+
+
+class TabulatedTidalTurbineOptions(TidalTurbineOptions):
+    """Options for tidal turbine with tabulated thrust coefficient (options.py:493-504): the first and the last speed are the
+    cut-in and the cut-out speed."""
+    name = 'Tabulated tidal turbine options'
+    _spec = OrderedDict([
+        ('thrust_speeds', (lambda: [0.9, 1., 3., 5., 5.001], _float_list)),
+        ('thrust_coefficients', (lambda: [0.01, 0.7, 0.7, 0.1, 0.0001], _float_list)),
+        ('power_coefficients', (None, _float_list_or_none)),
+    ])
+
+
+class TidalTurbineFarmOptions(FrozenOptions):
+    """Tidal turbine farm options (options.py:507-521): ``turbine_type`` 'constant' | 'table' paired with ``turbine_options``.
+    ``turbine_density``: a Constant / number, or a CG-P1 or DG-P1 ``Function``."""
+    name = 'Farm options'
+    _spec = OrderedDict([
+        ('turbine_density', (lambda: Constant(0.0), _scalar_expr_or_none)),
+        ('break_even_wattage', (0.0, _nonneg_float)),
+        # the reference reads this with getattr(options, 'upwind_correction', False) (turbines.py:155) and declares the trait on
+        # the discrete farm only; declared here with that default, so that a continuous farm can switch the correction on
+        ('upwind_correction', (False, _bool)),
+        ('turbine_type', ('constant', _enum('constant', 'table'))),
+    ])
+    _paired = {'turbine_type': ('turbine_options', OrderedDict([('constant', ConstantTidalTurbineOptions),
+                                                                ('table', TabulatedTidalTurbineOptions)]))}
+
+    def __init__(self):
+        object.__setattr__(self, 'turbine_options', None)
+        super().__init__()
+
+
+class DiscreteTidalTurbineFarmOptions(TidalTurbineFarmOptions):
+    """Discrete farm options (options.py:524-531).  Selectable for API fidelity; the device path raises for it (the bump
+    densities need the degree-10 rule of ``quadrature_degree``)."""
+    name = 'Discrete Farm options'
+    _spec = OrderedDict([
+        ('turbine_coordinates', (list, _any)),
+        ('upwind_correction', (True, _bool)),
+        ('quadrature_degree', (10, _nonneg_int)),
+    ])
+
+
 class CommonModelOptions(FrozenOptions):
     """Options that are common for both 2d and 3d models (options.py:583-733), hot-path subset + API names."""
     name = 'Model options'
@@ -291,6 +378,9 @@ class ModelOptions2d(CommonModelOptions):
         ('tracer_element_family', ('dg', _enum('dg', 'cg'))),
         ('use_supg_tracer', (False, _bool)),
         ('tracer_picard_iterations', (1, _nonneg_int)),
+        # subdomain id (``Mesh2d.cell_markers``) or 'everywhere' -> [farm options, ...] (options.py:1004-1011, solver2d.py:462-483)
+        ('tidal_turbine_farms', (dict, _any)),
+        ('discrete_tidal_turbine_farms', (dict, _any)),
         # paired enums last so that their slaves exist after construction
         ('swe_timestepper_type', ('CrankNicolson', _enum(*_SWE_STEPPERS))),
         ('tracer_timestepper_type', ('CrankNicolson', _enum(*_TRACER_STEPPERS))),

@@ -219,6 +219,8 @@ def build_partition(mesh, owner, rank, halo_depth=3, adjacency='facet'):
     part.cell_nbr = np.ascontiguousarray(mapped.astype(np.int32))
     part.cell_nbr_facet = np.ascontiguousarray(mesh.cell_nbr_facet[local_global])
     part.boundary_len = dict(mesh.boundary_len)
+    # a rank's cells keep their subdomain ids (tidal turbine farms)
+    part.cell_markers = np.ascontiguousarray(np.asarray(getattr(mesh, 'cell_markers', np.zeros(mesh.num_cells, dtype=np.int32)))[local_global])
     part.boundary_markers = mesh.boundary_markers
 
     # send lists (segments of one buffer, by peer) and receive lists (local ghost ids in the order the peer sends them)

@@ -126,6 +126,7 @@ class ERKGenericShuOsher(TimeIntegrator):
             device_id=device_id, boundary_len=getattr(mesh, 'boundary_len', None))
         self._uploaded_version = None
         self._device_ahead = False
+        self._farm_signatures = {}               # farm index -> signature of the density uploaded last (_push_farms)
         if equation.depth.use_wetting_and_drying:
             alpha = equation.depth.wetting_and_drying_alpha
             if isinstance(alpha, Function):
@@ -136,6 +137,7 @@ class ERKGenericShuOsher(TimeIntegrator):
                 alpha = float(alpha)
             self.device.set_wetting_and_drying(alpha)
         self._push_fields()
+        self._push_farms()
         self._push_bcs()
         uv, eta = self.solution.subfunctions
         uv._pull_hook = self._pull_solution
@@ -217,6 +219,29 @@ class ERKGenericShuOsher(TimeIntegrator):
                 dev.set_viscosity(None)
         self._field_signatures = new
 
+    def _push_farms(self):
+        """Upload the tidal turbine farms whose density changed since the last upload (a ``Function.assign`` or a new density between
+        two ``iterate`` calls: the Function's host version / the Constant's value, as the coefficient fields)"""
+        farms = getattr(self.equation, 'tidal_farms', None)
+        if not farms:
+            return
+        if self.comm is not None and self.comm.size > 1:
+            raise NotImplementedError('tidal_turbine_farms on several ranks: the partitioned driver does not carry turbine farms yet '
+                                      '(run the farm script on one device)')
+        if not hasattr(self.device, 'turbine_farm_set'):
+            raise NotImplementedError('tidal_turbine_farms: this device class has no turbine farms')
+        for i, farm in enumerate(farms):
+            sig = farm.density_signature()
+            if self._farm_signatures.get(i) != sig:
+                self.device.turbine_farm_set(i, farm.device_params(), farm.density_nodal())
+                self._farm_signatures[i] = sig
+
+    def turbine_power(self):
+        """instantaneous power of every farm (list), of the device-resident state"""
+        self._sync_to_device()
+        n = len(getattr(self.equation, 'tidal_farms', None) or [])
+        return [float(v) for v in self.device.turbine_power()[:n]]
+
     def _set_field(self, fid, v, vector=False):
         """Upload one coefficient field; a continuous (CG-P1) Function goes as one value per vertex and is injected into the
         DG nodes on the device (the cheap path for forcing fields that ``update_forcings`` changes every step)."""
@@ -296,6 +321,7 @@ class ERKGenericShuOsher(TimeIntegrator):
             self._device_ahead = False
 
     def _sync_to_device(self):
+        self._push_farms()
         if self._uploaded_version != self._host_version():
             self._pull_solution()           # no-op unless the device is ahead (then host edits win on top of it)
             self._push_solution()

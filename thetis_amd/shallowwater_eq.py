@@ -9,6 +9,7 @@ configuration is one the kernel implements:
   ExternalPressureGradientTerm :335   HUDivTerm :396   HorizontalAdvectionTerm :453 (+ Lax-Friedrichs)
   CoriolisTerm :619   AtmosphericPressureTerm :652   QuadraticDragTerm :666 (constant C_D or Manning)
   LinearDragTerm :728   MomentumSourceTerm :794   ContinuitySourceTerm :814   WindStressTerm :637   BoundaryDragTerm :704
+  TurbineDragTerm :765 (tidal turbine farms on cell subdomains, thetis_amd/turbines.py)
   HorizontalViscosityTerm :513 (SIPG; separate pass kernels csrc/swe2d_sipg.h, Constant or CG-P1 viscosity)
   boundary conditions 'elev' / 'uv' / 'un' / 'flux' with constant values (get_bnd_functions :232-272)
 """
@@ -38,15 +39,15 @@ class ShallowWaterEquations(object):
     SUPPORTED_TERMS = ('ExternalPressureGradientTerm', 'HorizontalAdvectionTerm', 'CoriolisTerm',
                        'AtmosphericPressureTerm', 'QuadraticDragTerm', 'LinearDragTerm', 'MomentumSourceTerm',
                        'HUDivTerm', 'ContinuitySourceTerm', 'WindStressTerm', 'BoundaryDragTerm',
-                       'HorizontalViscosityTerm')
+                       'HorizontalViscosityTerm', 'TurbineDragTerm')
 
     def __init__(self, function_space, depth, options, tidal_farms=None):
         self.function_space = function_space
         self.mesh = function_space.mesh()
         self.depth = depth
         self.options = options
-        if tidal_farms:
-            raise NotImplementedError('TurbineDragTerm is outside the device hot path')
+        # TurbineDragTerm (shallowwater_eq.py:765-791): part of the stage kernels' source-term code (csrc/swe2d_kernels.h: swe_farm_terms)
+        self.tidal_farms = tidal_farms
         if options.element_family != 'dg-dg' or options.polynomial_degree != 1:
             raise NotImplementedError("the device path implements element_family='dg-dg', polynomial_degree=1 only "
                                       "(got {!r}, degree {:})".format(options.element_family, options.polynomial_degree))

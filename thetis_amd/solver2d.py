@@ -197,7 +197,13 @@ class FlowSolver2d(object):
         if not hasattr(self.fields, 'uv_2d'):
             self.create_fields()
         self.equations = AttrDict()
-        self.equations.sw = ShallowWaterEquations(self.function_spaces.H_2d, self.depth, self.options)
+        # tidal farms, if any (solver2d.py:461-485)
+        from .turbines import build_farms
+        self.tidal_farms = build_farms(self.options, self.mesh2d)
+        for i, farm in enumerate(self.tidal_farms or []):
+            farm._solver, farm._index = self, i
+        self.equations.sw = ShallowWaterEquations(self.function_spaces.H_2d, self.depth, self.options,
+                                                  tidal_farms=self.tidal_farms)
         self.equations.sw.bnd_functions = self.bnd_functions['shallow_water']
         self.solve_tracer = len(self.options.tracer) > 0
         for label in self.options.tracer:
@@ -451,6 +457,7 @@ class FlowSolver2d(object):
         # per-time-step callbacks keep the steps batched when every one of them is a device detector (callback.DetectorsCallback):
         # the device appends a row after every step, the rows are handed over after the batch - the times and values of the
         # step-by-step loop.  Anything else (a host callback, several ranks) takes the step-by-step loop.
+        # (a TurbineFunctionalCallback appends power rows the same way)
         batch_rows = bool(step_cbs) and self.comm.size == 1 and all(hasattr(cb, 'row_probe') for cb in step_cbs)
         can_batch = (_batch and update_forcings is None and hasattr(stepper, 'advance_steps')
                      and (not step_cbs or (batch_rows and all(cb.row_probe(1) is not None for cb in step_cbs))))

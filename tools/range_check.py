@@ -26,9 +26,10 @@ def exercise():
         mesh, bath, uv, eta = case
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
-        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers'):
-            dev = Swe2dDevice(mesh, bath if variant != 'wetting-drying' else bath - 0.6*bath.max(), 0.05,
-                              boundary_len=mesh.boundary_len)
+        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying'):
+            # (farms: deep water, so that the radicand of the upwind correction stays positive)
+            bath_v = bath - 0.6*bath.max() if variant == 'wetting-drying' else (bath + 20.0 if variant.startswith('farms') else bath)
+            dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
             markers = mesh.boundary_markers
             if variant == 'open+fields':
                 dev.set_bc(markers[0], {'elev': 0.2*np.sin(cxy[:, :, 1]/3e3)})
@@ -43,7 +44,40 @@ def exercise():
             if variant == 'wetting-drying':
                 dev.set_wetting_and_drying(0.5)
                 dev.set_scalar(_lib.SCALAR_MANNING_DRAG, 0.02)
+            if variant.startswith('farms'):
+                # tidal turbine farms: the density planes and the farm-cell list are read through the checked loads (stage kernels and
+                # swe_turbine_power_kernel); the farms' constant table is read through plain pointers and the power rows are written
+                # with atomics - those accesses are not seen by the check (host-checked sizes: one SweFarmTable, capacity + 1 rows)
+                if variant == 'farms':
+                    dev.set_scalar(_lib.SCALAR_QUADRATIC_DRAG, 0.0025)
+                else:
+                    dev.set_wetting_and_drying(0.5)
+                    dev.set_scalar(_lib.SCALAR_MANNING_DRAG, 0.02)
+                xc = cxy[:, :, 0].mean(axis=1)
+                half = xc > np.median(xc)
+                par = _lib.TurbineParams()
+                par.rotor_area, par.projected_diameter, par.rho0, par.upwind_correction = 254.0, 18.0, 1000.0, 1
+                par.n_table = 5
+                for j, (sp, ct) in enumerate(zip([0.01, 0.02, 0.05, 0.08, 0.1], [0.01, 0.7, 0.7, 0.1, 0.0001])):
+                    par.speeds[j], par.thrust[j], par.power[j] = sp, ct, 0.5*ct
+                dev.turbine_farm_set(0, par, np.where(half[:, None], 2e-5, 0.0)*np.ones((mesh.num_cells, k)))
+                par2 = _lib.TurbineParams()
+                par2.rotor_area, par2.projected_diameter, par2.rho0 = 254.0, 18.0, 1000.0
+                par2.thrust_area_const, par2.power_const, par2.support_area = 0.8*254.0, 0.4, 5.0
+                dens = 1e-5*np.ones((mesh.num_cells, k))
+                dens[-1] = 0.0                       # ... whose farm-cell list ends one short of the last cell
+                dev.turbine_farm_set(3, par2, dens)
+                assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
             dev.set_state(0.1*uv, 0.1*np.abs(eta))
+            if variant.startswith('farms'):
+                dev.turbine_rows_reserve(3)
+                for _ in range(3):
+                    dev.advance(1)
+                    dev.turbine_rows_append()
+                rows = dev.turbine_rows_read()
+                assert rows.shape[0] == 3 and np.isfinite(rows).all() and (rows[:, [0, 3]] >= 0).all() and rows[:, 3].min() > 0, rows
+                assert np.isfinite(dev.turbine_power()).all()
+                n_launch += 8
             if variant == 'tracers':
                 tid = dev.add_tracer()
                 dev.tracer_set_state(tid, 1.0 + 0.1*np.random.default_rng(0).normal(size=(mesh.num_cells, k)))
