@@ -252,18 +252,20 @@ extern "C" {
 
 int swe2d_abi_version(void) { return SWE2D_ABI_VERSION; }
 
-static bool advance_takes_flow(Handle *h);
 int swe2d_fused_pair_info(swe2d_handle *hh, int32_t out[4])
 {
     Handle *h = H(hh);
     if (!h || !out) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     out[0] = out[1] = out[2] = 0; out[3] = h->n_cells;
     // (small whole meshes: swe2d_advance takes the dataflow kernel first; a partition's stage pairs are driven by the host)
-    if (!fuse12_covers(h) || (h->n_owned == h->n_cells && advance_takes_flow(h))) return SWE2D_OK;
+    const StepCaller who = h->n_owned == h->n_cells ? kAdvance : kPartitionPair;
+    StepPath path = step_plan(h, who);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = fuse12_build(h)) return rc;
-    if (h->npc == 4) { if (h->fuseq_tile) { out[0] = 1; out[1] = h->fuseq_n_tiles; out[2] = (int32_t)h->fuseq_ring_cells; } }
-    else if (h->fuse_tile) { out[0] = 1; out[1] = h->fuse_n_tiles; out[2] = (int32_t)h->fuse_ring_cells; }
+    if (path != kFlow) { if (int rc = step_ready(h, who, kPair, &path)) return rc; }
+    if (path != kPair) return SWE2D_OK;
+    out[0] = 1;
+    if (h->npc == 4) { out[1] = h->fuseq_n_tiles; out[2] = (int32_t)h->fuseq_ring_cells; }
+    else { out[1] = h->fuse_n_tiles; out[2] = (int32_t)h->fuse_ring_cells; }
     return SWE2D_OK;
 }
 
@@ -594,7 +596,7 @@ int swe2d_set_state(swe2d_handle *hh, const double *uv, const double *eta)
         HIP_TRY(h, hipGetLastError());
     }
     h->state_holds_D = h->wd;                      // wetting-drying: the elevation planes now hold the displaced depth D
-    h->stage_valid[0] = h->stage_valid[1] = false; // no stage of this state has run yet
+    stage_invalidate(h);                           // no stage of this state has run yet
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
     return SWE2D_OK;
 }
@@ -620,7 +622,7 @@ int swe2d_state_snapshot_slot(swe2d_handle *hh, int slot, int restore)
         for (size_t t = 0; t < h->tracers.size(); t++)
             HIP_TRY(h, hipMemcpyAsync(h->tracers[t].buf[0], (char *)sn.data + nb + t*nt, nt, hipMemcpyDeviceToDevice, h->stream));
         h->state_holds_D = sn.holds_D;
-        h->stage_valid[0] = h->stage_valid[1] = false;     // the stage buffers belong to the steps that are being undone
+        stage_invalidate(h);                               // the stage buffers belong to the steps that are being undone
         return SWE2D_OK;
     }
     if (sn.data && sn.bytes != total) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(sn.data); sn.data = nullptr; }
@@ -900,12 +902,6 @@ int swe2d_solve_stage(swe2d_handle *hh, int i_stage)
     return swe2d_solve_stage_cells(hh, i_stage, 0, h->n_owned);
 }
 
-// does swe2d_advance run this handle's steps in the dataflow kernel?
-static bool advance_takes_flow(Handle *h)
-{
-    return opt_on(h, SWE2D_OPT_FLOW) && flow_kernel_covers(h) && ((h->flow_blocks + 7)/8)*8 <= flow_capacity(h);
-}
-
 int swe2d_advance(swe2d_handle *hh, int n_steps)
 {
     Handle *h = H(hh);
@@ -915,28 +911,8 @@ int swe2d_advance(swe2d_handle *hh, int n_steps)
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance");
-    // Up to 128 steps per launch without grid barriers (swe2d_flow.h) where every 64-cell block of the mesh is resident at once
-    // (<= 131 k cells) and the kernel covers the configuration.  Same box, us/step, three stage launches per step -> flow launches:
-    // 15 k cells 16.5 -> 15.3, 62 k 20.1 -> 15.1, 125 k 24.3 -> 18.3 (the one-launch step kernel of round 2, which this replaces:
-    // 14.1 / 16.8 / 24.9).  SWE2D_OPT_FLOW = 0 selects the stage launches (the same bits either way).
-    {
-        if (n_steps > 0 && advance_takes_flow(h)) {
-            int32_t ends[SWE_FLOW_MAX_STAGES];
-            for (int s = 0; s < SWE_FLOW_MAX_STAGES; s++) ends[s] = h->n_owned;
-            for (int done = 0; done < n_steps;) {
-                const int m = std::min(n_steps - done, SWE_FLOW_MAX_STAGES/3);
-                int rc = launch_flow(h, 3*m, ends);
-                if (rc) return rc;
-                done += m;
-            }
-            return SWE2D_OK;
-        }
-    }
-    // stages 1 and 2 in one launch by overlapped tiles (swe2d_fuse.h) + stage 3 as a stage launch where that kernel covers the
-    // handle, three stage launches otherwise: the same bits (step_swe, swe2d_api_fuse.hip)
-    for (int it = 0; it < n_steps; it++)
-        if (int rc = step_swe(h)) return rc;
-    return SWE2D_OK;
+    // the dataflow kernel, the three-stage kernel, the fused stage pair + stage 3 or three stage launches: the same bits (swe2d_plan.hip)
+    return step_swe(h, kAdvance, n_steps);
 }
 
 int swe2d_advance_forward_euler(swe2d_handle *hh, int n_steps)
@@ -948,10 +924,8 @@ int swe2d_advance_forward_euler(swe2d_handle *hh, int n_steps)
     if (int rc = capture_parity_check(h)) return rc;
     for (int it = 0; it < n_steps; it++) {
         // U_new = U + dt M^-1 R(U): stage 0 of the Shu-Osher form; the result becomes buffer A by a pointer swap
-        int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, 0, h->n_owned);
-        if (rc) return rc;
-        std::swap(h->state[0], h->state[1]);
-        h->stage_valid[0] = h->stage_valid[1] = false;     // buffer B now holds the state before the step, not a stage solution
+        if (int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, 0, h->n_owned)) return rc;
+        swap_state_buffers(h);                             // buffer B now holds the state before the step, not a stage solution
     }
     return SWE2D_OK;
 }
@@ -967,7 +941,7 @@ int swe2d_forward_euler_cells(swe2d_handle *hh, int32_t cell_begin, int32_t cell
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     if (int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, cell_begin, cell_end)) return rc;
-    h->stage_valid[0] = h->stage_valid[1] = false;         // a ForwardEuler step leaves no SSPRK33 stage solution
+    stage_invalidate(h);                                   // a ForwardEuler step leaves no SSPRK33 stage solution
     return SWE2D_OK;
 }
 
@@ -976,8 +950,7 @@ int swe2d_swap_state_buffers(swe2d_handle *hh)
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (int rc = capture_parity_check(h)) return rc;
-    std::swap(h->state[0], h->state[1]);
-    h->stage_valid[0] = h->stage_valid[1] = false;
+    swap_state_buffers(h);
     return SWE2D_OK;
 }
 
@@ -991,33 +964,30 @@ int swe2d_advance_timed(swe2d_handle *hh, int n_steps, int per_launch, float *ms
     if (int rc = capture_parity_check(h)) return rc;
     if (!per_launch) {
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        int rc = swe2d_advance(hh, n_steps);
-        if (rc) return rc;
+        if (int rc = swe2d_advance(hh, n_steps)) return rc;
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
         HIP_TRY(h, hipEventSynchronize(h->ev1));
         HIP_TRY(h, hipEventElapsedTime(ms_total, h->ev0, h->ev1));
         if (ms_kernel_avg) *ms_kernel_avg = *ms_total/(3.0f*n_steps);
         return SWE2D_OK;
     }
-    // events around every launch of a step, on the launch stream: three stage launches, the fused stage pair + stage 3, or the one
-    // launch of all three stages (the mean is per element-update - a third of a step - in every case)
-    const bool triple = fuse123_wanted(h);
-    if (!triple && fuse12_covers(h)) { if (int rc = fuse12_build(h)) return rc; }
-    const bool fused = !triple && fuse12_covers(h) && (h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr);
-    const int lps = triple ? 1 : (fused ? 2 : 3);
-    const int nl = lps*n_steps;
-    std::vector<hipEvent_t> ev(2*(size_t)nl);
+    // events around every launch of a step, on the launch stream: the launches step_swe makes (the mean is per element-update - a
+    // third of a step - in every case)
+    StepPath path;
+    if (int rc = whole_step_path(h, kWholeStep, &path)) return rc;
+    const int lps = launches_per_step(path), nl = lps*n_steps;
+    struct Events {                                          // (released on every way out)
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } events{std::vector<hipEvent_t>(2*(size_t)nl, nullptr)};
+    auto &ev = events.ev;
     for (auto &e : ev) HIP_TRY(h, hipEventCreate(&e));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    int l = 0;
-    for (int it = 0; it < n_steps; it++)
-        for (int s = 0; s < lps; s++, l++) {
-            HIP_TRY(h, hipEventRecord(ev[2*l], h->stream));
-            int rc = triple ? launch_fuse123(h, h->n_owned)
-                            : (fused ? (s == 0 ? launch_fuse12(h, h->n_owned) : stage_on_range(h, 2, 0, h->n_owned)) : stage_on_range(h, s, 0, h->n_owned));
-            if (rc) return rc;
-            HIP_TRY(h, hipEventRecord(ev[2*l + 1], h->stream));
-        }
+    for (int l = 0; l < nl; l++) {
+        HIP_TRY(h, hipEventRecord(ev[2*l], h->stream));
+        if (int rc = step_launch(h, path, l % lps)) return rc;
+        HIP_TRY(h, hipEventRecord(ev[2*l + 1], h->stream));
+    }
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     HIP_TRY(h, hipEventSynchronize(h->ev1));
     HIP_TRY(h, hipEventElapsedTime(ms_total, h->ev0, h->ev1));
@@ -1027,7 +997,6 @@ int swe2d_advance_timed(swe2d_handle *hh, int n_steps, int per_launch, float *ms
         HIP_TRY(h, hipEventElapsedTime(&ms, ev[2*i], ev[2*i + 1]));
         sum += ms;
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     if (ms_kernel_avg) *ms_kernel_avg = (float)(sum/(3.0*n_steps));
     return SWE2D_OK;
 }
@@ -1048,9 +1017,8 @@ int swe2d_tendency(swe2d_handle *hh, double *k_uv, double *k_eta)
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     // k into buffer B: U_out = 1*k + 0*U0 + 0*U_in
-    int rc = launch_stage(h, 0, 0, 1, 0.0, 0.0, 1.0, 0, h->n_owned);
-    if (rc) return rc;
-    h->stage_valid[0] = false;                               // buffer B holds the tendency, not a stage solution
+    if (int rc = launch_stage(h, 0, 0, 1, 0.0, 0.0, 1.0, 0, h->n_owned)) return rc;
+    stage_written(h, false, h->stage_valid[1]);              // buffer B holds the tendency, not a stage solution
     const size_t n = (size_t)h->n_cells*h->npc;
     hipLaunchKernelGGL(swe_planes_to_aos, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream,
                        h->state[1], h->stage_uv, h->stage_eta, h->stride, h->n_cells, h->npc);

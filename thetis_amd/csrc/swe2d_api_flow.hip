@@ -118,15 +118,6 @@ int flow_build(Handle *h, const int32_t *order)
     return SWE2D_OK;
 }
 
-// the configurations the flow kernel covers: triangles, no viscosity; wetting-drying since round 5 (swe_flow_kernel<..., WD>, nonlinear
-// equations as in the stage kernels; SWE2D_OPT_FLOW_WD = 0 leaves it to the stage launches)
-bool flow_kernel_covers(const Handle *h)
-{
-    if (h->wd && (!h->par.use_nonlinear_equations || !opt_on(h, SWE2D_OPT_FLOW_WD))) return false;
-    if (h->n_farms > 0) return false;                        // tidal turbine farms: stage launches (swe_source_terms<true>)
-    return h->npc == 3 && !h->visc && h->idx4 && h->flow_flag && h->flow_ex && h->opt[SWE2D_OPT_BND_INLINE] != 0;
-}
-
 // Resident one-wave workgroups of the flow kernel: every block of a launch must be resident (a block waits for its
 // neighbours' flags), so the grid must not exceed what the device holds at once.
 int flow_capacity(Handle *h)
@@ -179,7 +170,7 @@ int flow_build_exchange(Handle *h)
 // n_stages stages each with the peer-to-peer halo exchange (channel 0) inside the launch
 int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles)
 {
-    if (!flow_kernel_covers(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "the flow kernel covers triangles without viscosity (wetting-drying: nonlinear equations)");
+    if (!(step_kernels(h) & kFlow)) return fail(h, SWE2D_ERR_UNSUPPORTED, "the flow kernel covers triangles without viscosity (wetting-drying: nonlinear equations)");
     const bool fx = n_cycles > 0;
     const int total = n_stages*(fx ? n_cycles : 1);
     if (n_stages <= 0 || n_stages % 3 != 0 || total > SWE_FLOW_MAX_STAGES || n_cycles > SWE_FLOW_MAX_CYCLES)
@@ -188,7 +179,7 @@ int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles)
         if (cell_end[s] < 0 || cell_end[s] > h->n_cells || (s > 0 && cell_end[s] > cell_end[s - 1]))
             return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "flow: the stage ranges must shrink and stay inside the mesh");
     const int grid = ((h->flow_blocks + 7)/8)*8;
-    if (grid > flow_capacity(h))
+    if (!flow_fits(h))
         return fail(h, SWE2D_ERR_UNSUPPORTED, "flow: more 64-cell blocks than the device holds resident at once");
     SweFlowArgs q{};
     if (fx) {
@@ -243,11 +234,7 @@ int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles)
     // (peers inside one process must run side by side; across processes DistributedSwe2d does not choose the flow path by itself
     // when ranks share a device), and so are launches under stream capture (one handle per graph).
     bool chained = false;
-    if (!fx) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = h->stream && hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-        chained = !capturing && h->device >= 0 && h->device < kFlowChainDevices;
-    }
+    if (!fx) chained = !stream_capturing(h) && h->device >= 0 && h->device < kFlowChainDevices;
     std::unique_lock<std::mutex> lock(g_flow_chain_mu, std::defer_lock);
     if (chained) {
         lock.lock();
@@ -263,7 +250,7 @@ int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles)
         fc.last_uid = h->uid;
     }
     h->flow_used = true;
-    h->stage_valid[0] = h->stage_valid[1] = false;           // the stage solutions stay in registers
+    stage_invalidate(h);                                     // the stage solutions stay in registers
     return SWE2D_OK;
 }
 
@@ -271,8 +258,7 @@ int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles)
 int flow_check(Handle *h)
 {
     if (!h->flow_used || !h->flow_status) return SWE2D_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (h->stream && hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return SWE2D_OK;
+    if (stream_capturing(h)) return SWE2D_OK;
     unsigned st[2] = {0u, 0u};
     HIP_TRY(h, hipMemcpyAsync(st, h->flow_status, sizeof(st), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -354,9 +340,9 @@ int swe2d_flow_set_order(swe2d_handle *hh, const int32_t *cells_in_flow_order)
 int swe2d_flow_supported(swe2d_handle *hh)
 {
     Handle *h = H(hh);
-    if (!h || !flow_kernel_covers(h)) return 0;
+    if (!h || !(step_kernels(h) & kFlow)) return 0;
     if (hipSetDevice(h->device) != hipSuccess) return 0;
-    return ((h->flow_blocks + 7)/8)*8 <= flow_capacity(h) ? (has_sources(h) ? 1 : 2) : 0;
+    return flow_fits(h) ? (has_sources(h) ? 1 : 2) : 0;
 }
 
 int swe2d_flow_status(swe2d_handle *hh, int32_t *timeouts)

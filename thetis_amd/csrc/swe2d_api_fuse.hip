@@ -15,37 +15,6 @@ fuse_kernel_t pick_fuse_src(bool nl, bool lf)
 fuse_kernel_t pick_fuse_kernel(bool nl, bool lf, bool src) { return src ? pick_fuse_src<true>(nl, lf) : pick_fuse_src<false>(nl, lf); }
 }  // namespace
 
-// What the kernel covers: triangles, no wetting-drying, no viscosity - with or without source terms (the SRC instances keep the 168
-// VGPRs / three workgroups per CU of the plain ones, tools/kres.py), the whole mesh or a partition's owned + ghost cells on its
-// shrinking stage ranges (round 6); taken from
-// 250 k cells, where a step streams from memory (same box, us per step, stage launches -> fused pair + stage 3, device numbering in
-// 16 x 6-quad tiles: 125 k cells 23.9 -> 24.1, 250 k 38.8 -> 37.0, 500 k 64.9 -> 61.1, 1 M 121.0 -> 107.3, 2 M 264 -> 235, 4 M 525 -> 477;
-// profiles/r05zl_fused_stage_pair.txt), and where the numbering gives tiles worth it (mean interior >= 176 of 192 cells: the
-// structured tile order, and the Hilbert order of an unstructured mesh - 1 M Delaunay triangles 192.0 + 49.9 cells per tile, 120.8 ->
-// 113.3 us per step; an order that does not keeps its stage launches).
-// SWE2D_OPT_FUSED_STAGES = 0: never; = 1: on every mesh (of at least 64 cells) whatever its tiles.  (In the range-checked build too since
-// round 6: the shared functions test their LDS indices against the array they are handed, the tile tables are host-built indices.)
-static bool fuse_applies(const Handle *h)                      // what every fused kernel needs, whatever the size
-{
-    if (h->opt[SWE2D_OPT_FUSED_STAGES] == 0) return false;
-    if (h->opt[SWE2D_OPT_BND_INLINE] == 0) return false;     // the epilogue variant was asked for
-    if (h->n_farms > 0) return false;                        // tidal turbine farms: the stage kernels carry the term, the tiles do not
-    return !h->wd && !h->visc && !h->h_nbr.empty();
-}
-
-bool fuse12_covers(const Handle *h)
-{
-    const int mode = h->opt[SWE2D_OPT_FUSED_STAGES];         // -1, 2: by size and tile quality; 1, 3: forced
-    if (!fuse_applies(h) || h->fuse_state == -1) return false;
-    const bool forced = mode == 1 || mode == 3;
-    // triangles: whole meshes and partitions, from 250 k cells
-    if (h->npc == 3) return h->idx4 != nullptr && h->n_cells >= (forced ? 64 : 250000);
-    // quadrilaterals (swe_fuse12_quad_kernel, round 6): whole meshes, from the size at which the three state buffers (3 x 96 B per cell)
-    // leave the Infinity Cache - same box, us per step without -> with: 1 M cells 188.9 -> 172.6, + Manning 221.1 -> 212.0, cfg 4 338.8 ->
-    // 329.3; 640 k cells 115.7 -> 114.6, + Manning 136.8 -> 142.7 (profiles/r06g_quads*.txt)
-    return h->n_owned == h->n_cells && h->n_cells >= (forced ? 64 : 850000);
-}
-
 // Tiles: consecutive cells of the device numbering (compact patches in the tile-Hilbert order) - or of the order handed in with
 // swe2d_fused_set_order: a partition's ghost layers are appended to its numbering layer by layer, strips one cell wide whose tiles
 // would be all ring - as long as the interior holds at most 192 cells and the ring - every cell that shares a facet with an
@@ -54,12 +23,8 @@ int fuseq_build(Handle *h);
 int fuse12_build(Handle *h)
 {
     if (h->npc == 4) return fuseq_build(h);
-    if (h->fuse_tile || h->fuse_state == -1) return SWE2D_OK;
-    {   // allocations and copies: not inside a stream capture - such a capture keeps the stage launches, the next call outside one builds
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return SWE2D_OK;
-        (void)hipGetLastError();
-    }
+    // allocations and copies: not inside a stream capture - such a capture keeps the stage launches, the next call outside one builds
+    if (h->fuse_tile || h->fuse_state == -1 || stream_capturing(h)) return SWE2D_OK;
     const int n = h->n_cells;
     const size_t S = h->stride;
     const int *nbr = h->h_nbr.data();
@@ -124,13 +89,7 @@ int fuse12_build(Handle *h)
         for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
     }
     h->fuse_n_tiles = (int)inner.size();
-    // tiles not worth it: the mean interior below 176 of 192 cells on a whole mesh, below 150 on a partition (its tiles along the cuts
-    // and through the ghost layers are partial by construction)
-    const bool forced = h->opt[SWE2D_OPT_FUSED_STAGES] == 1 || h->opt[SWE2D_OPT_FUSED_STAGES] == 3;
-    if (!forced && (double)n/h->fuse_n_tiles < (h->n_owned == h->n_cells ? 176.0 : 150.0)) {
-        h->fuse_state = -1; h->fuse_n_tiles = 0;
-        return SWE2D_OK;
-    }
+    if (!fuse12_tiles_pay(h, h->fuse_n_tiles)) { h->fuse_state = -1; h->fuse_n_tiles = 0; return SWE2D_OK; }
     HIP_TRY(h, hipMalloc(&h->fuse_tile, tl.size()*sizeof(int2)));
     HIP_TRY(h, hipMalloc(&h->fuse_inner, inner.size()*sizeof(int)));
     HIP_TRY(h, hipMemcpy(h->fuse_tile, tl.data(), tl.size()*sizeof(int2), hipMemcpyHostToDevice));
@@ -144,8 +103,7 @@ int launch_fuse12_quad(Handle *h, int cell_end);
 int launch_fuse12(Handle *h, int cell_end)
 {
     if (h->npc == 4) return launch_fuse12_quad(h, cell_end);
-    if (int rc = fuse12_build(h)) return rc;
-    if (!h->fuse_tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stage pair: no tile tables");
+    if (!h->fuse_tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stage pair: no tile tables");     // (step_ready builds them)
     SweFuseArgs q;
     fill_stage_args(h, q.st, 0, 0, 2, 0.0, 1.0, kBeta[0], 0, h->n_owned);
     q.st.idxc = h->opt[SWE2D_OPT_COMPACT_IDX] == 0 ? nullptr : h->idxc;      // (the 16-B connectivity records: a streaming kernel)
@@ -168,12 +126,7 @@ int launch_fuse12(Handle *h, int cell_end)
 // ---- the stage pair on quadrilaterals (swe_fuse12_quad_kernel): tiles of up to 192 consecutive cells + their ring of at most 64
 int fuseq_build(Handle *h)
 {
-    if (h->fuseq_tile || h->fuse_state == -1) return SWE2D_OK;
-    {   // allocations and copies: not inside a stream capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return SWE2D_OK;
-        (void)hipGetLastError();
-    }
+    if (h->fuseq_tile || h->fuse_state == -1 || stream_capturing(h)) return SWE2D_OK;      // (allocations and copies: not inside a stream capture)
     const int n = h->n_cells;
     const size_t S = h->stride;
     const int *nbr = h->h_nbr.data();
@@ -234,8 +187,7 @@ int fuseq_build(Handle *h)
         for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
     }
     h->fuseq_n_tiles = (int)inner.size();
-    const bool forced = h->opt[SWE2D_OPT_FUSED_STAGES] == 1 || h->opt[SWE2D_OPT_FUSED_STAGES] == 3;
-    if (!forced && (double)n/h->fuseq_n_tiles < 176.0) { h->fuse_state = -1; h->fuseq_n_tiles = 0; return SWE2D_OK; }   // tiles not worth it
+    if (!fuse12_tiles_pay(h, h->fuseq_n_tiles)) { h->fuse_state = -1; h->fuseq_n_tiles = 0; return SWE2D_OK; }
     HIP_TRY(h, hipMalloc(&h->fuseq_tile, tl.size()*sizeof(int4)));
     HIP_TRY(h, hipMalloc(&h->fuseq_inner, inner.size()*sizeof(int)));
     HIP_TRY(h, hipMemcpy(h->fuseq_tile, tl.data(), tl.size()*sizeof(int4), hipMemcpyHostToDevice));
@@ -261,7 +213,6 @@ fuseq_kernel_t pick_fuseq_kernel(bool nl, bool lf, bool src, bool affine)
 
 int launch_fuse12_quad(Handle *h, int cell_end)
 {
-    if (int rc = fuseq_build(h)) return rc;
     if (!h->fuseq_tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stage pair: no tile tables");
     SweFuseQuadArgs q;
     fill_stage_args(h, q.st, 0, 0, 2, 0.0, 1.0, kBeta[0], 0, h->n_owned);
@@ -406,8 +357,7 @@ int launch_fuse123(Handle *h, int cell_end)
     SWE_CHK_SYNC(h->stream);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SWE_FUSE_WG), 0, h->stream, q);
     HIP_TRY(h, hipGetLastError());
-    std::swap(h->state[0], h->state[1]);
-    h->stage_valid[0] = h->stage_valid[1] = false;          // U(1) and U(2) never left the chip
+    swap_state_buffers(h);                                  // (U(1) and U(2) never left the chip)
     // inside a stream capture the swap is only the host's: a graph that holds an odd number of them ends on the other buffer than it
     // began on and cannot be replayed twice - counted per capture here, reported by capture_parity_check at the next call outside it
     unsigned long long id = 0;
@@ -428,7 +378,7 @@ int capture_parity_check(Handle *h)
     const bool capturing = stream_capturing(h, &id);
     if (h->capture_swaps) {
         if (capturing && id == h->capture_id) return SWE2D_OK;
-        if (h->capture_swaps & 1) { std::swap(h->state[0], h->state[1]); h->capture_odd++; }
+        if (h->capture_swaps & 1) { swap_state_buffers(h); h->capture_odd++; }
         h->capture_swaps = 0;
     }
     if (capturing || h->capture_odd == 0) return SWE2D_OK;
@@ -439,45 +389,19 @@ int capture_parity_check(Handle *h)
                 "capture); capture an even number per sequence");
 }
 
-// All three stages in one launch.  With tiles cut as consecutive cells of the numbering (147 + 52 + 57 per tile, ragged) the second ring
-// costs 1.26 x the arithmetic of the pair and only pays where the state no longer fits the Infinity Cache - same box, us per step,
-// three stage launches / fused pair + stage 3 / all three fused (profiles/r06b_fused_sizes.txt): 250 k cells 37.0 / 35.2 / 36.1,
-// 1 M 110.0 / 103.0 / 110.8, 2 M 272.0 / 233.3 / 229.9, 4 M 527.9 / 475.3 / 452.1: by itself from 2.5 M cells.  With the caller's
-// patches (swe2d_fused_set_triple_tiles: 11 x 8 quads of a RectangleMesh = 176 + 38 + 42 cells, every lane of the 256 used) it wins
-// wherever the dataflow kernel does not apply (profiles/r06l_triple_tiles.txt, r06m_triple_sizes.txt): 150 k cells 28.3 / 27.5 / 24.1,
-// 250 k 36.9 / 34.8 / 31.5, 500 k 62.4 / 57.9 / 53.8, 1 M - / 103.4 / 96.8, 2 M - / 235.4 / 207.5, 4 M - / 476.7 / 406.9: by itself from
-// 131 073 cells.  Not with source terms (those instances need 187-199 VGPRs: at three workgroups per CU they spill 80-132 B per lane - 1 M
-// cells 159-161 us per step by the pair, 235-239 by this kernel -, at two, as built, 195-196 against 163-164: profiles/r06q_*;
-// SWE2D_OPT_FUSED_STAGES = 3 forces it, = 2 keeps the pair at every size).
-// Whole meshes; not inside a stream capture (the launch swaps two state buffers on the host).
-bool fuse123_wanted(const Handle *h)
-{
-    const int mode = h->opt[SWE2D_OPT_FUSED_STAGES];
-    const bool patches = (int)h->fuse3_start.size() == h->n_cells;
-    const int from = patches ? 131073 : 2500000;              // (131 072 cells = 2048 resident blocks: what the dataflow kernel holds)
-    if (h->npc != 3 || !fuse_applies(h) || h->idx4 == nullptr || h->n_owned != h->n_cells) return false;
-    return mode == 3 ? h->n_cells >= 64 : (mode == -1 && h->n_cells >= from && !has_sources(h));
-}
+}  // namespace swe2d_impl
 
-// one SSPRK33 step of the shallow-water state on the whole mesh by the launches swe2d_advance would take when the dataflow kernel
-// does not apply: the fused stage pair + stage 3 where it covers the handle, three stage launches otherwise
-int step_swe(Handle *h)
+// a tile order handed in by the caller (null: none): a permutation of the cells
+static int checked_tile_order(Handle *h, const int32_t *cells, std::vector<int> &order)
 {
-    if (fuse123_wanted(h)) {
-        // all three stages in one launch (whole meshes; the launch swaps two state buffers on the host: not inside a stream capture)
-        if (!stream_capturing(h)) return launch_fuse123(h, h->n_owned);
+    std::vector<char> seen((size_t)h->n_cells, 0);
+    for (int i = 0; cells && i < h->n_cells; i++) {
+        if (cells[i] < 0 || cells[i] >= h->n_cells || seen[cells[i]]) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "fused stages: the tile order is not a permutation of the cells");
+        seen[cells[i]] = 1;
     }
-    if (fuse12_covers(h)) { if (int rc = fuse12_build(h)) return rc; }
-    if (fuse12_covers(h) && (h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr)) {
-        if (int rc = launch_fuse12(h, h->n_owned)) return rc;
-        return stage_on_range(h, 2, 0, h->n_owned);
-    }
-    for (int s = 0; s < 3; s++)
-        if (int rc = stage_on_range(h, s, 0, h->n_owned)) return rc;
+    if (cells) order.assign(cells, cells + h->n_cells);
     return SWE2D_OK;
 }
-
-}  // namespace swe2d_impl
 
 extern "C" {
 
@@ -487,15 +411,7 @@ int swe2d_fused_set_order(swe2d_handle *hh, const int32_t *cells_in_tile_order)
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     std::vector<int> order;
-    if (cells_in_tile_order) {
-        std::vector<char> seen((size_t)h->n_cells, 0);
-        for (int i = 0; i < h->n_cells; i++) {
-            const int c = cells_in_tile_order[i];
-            if (c < 0 || c >= h->n_cells || seen[c]) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "fused stages: the tile order is not a permutation of the cells");
-            seen[c] = 1;
-        }
-        order.assign(cells_in_tile_order, cells_in_tile_order + h->n_cells);
-    }
+    if (int rc = checked_tile_order(h, cells_in_tile_order, order)) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->fuse_tile) { (void)hipFree(h->fuse_tile); h->fuse_tile = nullptr; }
     if (h->fuse_inner) { (void)hipFree(h->fuse_inner); h->fuse_inner = nullptr; }
@@ -518,15 +434,7 @@ int swe2d_fused_set_triple_tiles(swe2d_handle *hh, const int32_t *cells_in_tile_
     HIP_TRY(h, hipSetDevice(h->device));
     std::vector<int> order;
     std::vector<unsigned char> start;
-    if (cells_in_tile_order) {
-        std::vector<char> seen((size_t)h->n_cells, 0);
-        for (int i = 0; i < h->n_cells; i++) {
-            const int c = cells_in_tile_order[i];
-            if (c < 0 || c >= h->n_cells || seen[c]) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "fused stages: the tile order is not a permutation of the cells");
-            seen[c] = 1;
-        }
-        order.assign(cells_in_tile_order, cells_in_tile_order + h->n_cells);
-    }
+    if (int rc = checked_tile_order(h, cells_in_tile_order, order)) return rc;
     if (n_starts < 0 || (n_starts > 0 && !tile_starts)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "fused stages: tile starts");
     if (n_starts > 0) {
         start.assign((size_t)h->n_cells, 0);
@@ -544,42 +452,22 @@ int swe2d_fused_set_triple_tiles(swe2d_handle *hh, const int32_t *cells_in_tile_
     return SWE2D_OK;
 }
 
-int swe2d_fused_triple_info(swe2d_handle *hh, int32_t out[4])
+// out[0] = 1 when `who` takes the three-stage kernel now (builds the tile tables; inside a stream capture nothing is built and the
+// answer is 0 while they are missing: the caller takes the stage launches), out[1] = tiles, out[2] / out[3] = cells of the two rings
+static int fused_triple_info(Handle *h, StepCaller who, int32_t out[4])
 {
-    Handle *h = H(hh);
     if (!h || !out) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!fuse123_wanted(h)) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = fuse123_build(h)) return rc;
-    if (!h->fuse3_tile) return SWE2D_OK;                      // not built (inside a stream capture)
+    StepPath path;
+    if (int rc = step_ready(h, who, kTriple, &path)) return rc;
+    if (path != kTriple) return SWE2D_OK;
     out[0] = 1; out[1] = h->fuse3_n_tiles; out[2] = (int32_t)h->fuse3_ring1; out[3] = (int32_t)h->fuse3_ring2;
     return SWE2D_OK;
 }
-
-// A partition's whole step in one launch: what swe2d_solve_step_cells needs (the rule is the caller's - see swe2d_fused_step_info)
-static bool fuse123_partition_ok(const Handle *h)
-{
-    const int mode = h->opt[SWE2D_OPT_FUSED_STAGES];
-    if (h->npc != 3 || !fuse_applies(h) || h->idx4 == nullptr || mode == 2 || mode == 1) return false;
-    return mode == 3 || !has_sources(h);
-}
-
-int swe2d_fused_step_info(swe2d_handle *hh, int32_t out[4])
-{
-    Handle *h = H(hh);
-    if (!h || !out) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
-    out[0] = out[1] = out[2] = out[3] = 0;
-    // by itself where the caller handed in patches (swe2d_fused_set_triple_tiles) and the cell range is beyond the dataflow kernel's
-    const int mode = h->opt[SWE2D_OPT_FUSED_STAGES];
-    if (!fuse123_partition_ok(h)) return SWE2D_OK;
-    if (mode != 3 && ((int)h->fuse3_start.size() != h->n_cells || h->n_cells <= 131072)) return SWE2D_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = fuse123_build(h)) return rc;
-    if (!h->fuse3_tile) return SWE2D_OK;                      // not built (inside a stream capture): the caller takes the stage launches
-    out[0] = 1; out[1] = h->fuse3_n_tiles; out[2] = (int32_t)h->fuse3_ring1; out[3] = (int32_t)h->fuse3_ring2;
-    return SWE2D_OK;
-}
+int swe2d_fused_triple_info(swe2d_handle *hh, int32_t out[4]) { return fused_triple_info(H(hh), kWholeStep, out); }
+// by itself where the caller handed in patches (swe2d_fused_set_triple_tiles) and the cell range is beyond the dataflow kernel's
+int swe2d_fused_step_info(swe2d_handle *hh, int32_t out[4]) { return fused_triple_info(H(hh), kPartitionStep, out); }
 
 // All three stages of a step on a partition: stage 3 on [0, cell_end) - the last of the step's three shrinking ranges; the tiles
 // evaluate stages 1 and 2 on supersets of theirs (every cell of a tile / interior + first ring), values that never leave the chip.
@@ -590,12 +478,12 @@ int swe2d_solve_step_cells(swe2d_handle *hh, int32_t cell_end)
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (cell_end < 0 || cell_end > h->n_cells) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell range");
-    if (!fuse123_partition_ok(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: the three-stage kernel does not cover this handle");
+    // (the caller's launch: whatever the size - swe2d_fused_step_info holds the rule)
+    if (!(step_kernels(h) & kTriple)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: the three-stage kernel does not cover this handle");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
-    if (!h->fuse3_tile) {           // tile tables: allocations and copies, not inside a stream capture
-        if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: first call inside a stream capture (swe2d_fused_step_info builds the tables)");
-    }
+    if (!h->fuse3_tile && stream_capturing(h))    // tile tables: allocations and copies, not inside a stream capture
+        return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_step_cells: first call inside a stream capture (swe2d_fused_step_info builds the tables)");
     return launch_fuse123(h, cell_end);
 }
 
@@ -609,8 +497,9 @@ int swe2d_solve_stage_pair_cells(swe2d_handle *hh, int32_t cell_end_0, int32_t c
     if (cell_end_1 < 0 || cell_end_1 > cell_end_0 || cell_end_0 > h->n_cells) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell ranges");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
-    if (fuse12_covers(h)) { if (int rc = fuse12_build(h)) return rc; }
-    if (fuse12_covers(h) && (h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr)) return launch_fuse12(h, cell_end_1);
+    StepPath path;
+    if (int rc = step_ready(h, kPartitionPair, kPair, &path)) return rc;
+    if (path == kPair) return launch_fuse12(h, cell_end_1);
     if (int rc = stage_on_range(h, 0, 0, cell_end_0)) return rc;
     return stage_on_range(h, 1, 0, cell_end_1);
 }

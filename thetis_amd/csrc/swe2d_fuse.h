@@ -1,5 +1,5 @@
 // swe2d_fuse.h - stages 1 and 2 of an SSPRK33 step in ONE launch by overlapped tiles.  What swe2d_advance takes by itself from
-// 250 k triangles on a whole mesh the kernel covers (swe2d_api_fuse.hip: fuse12_covers; SWE2D_OPT_FUSED_STAGES forces or forbids it).
+// 250 k triangles on a whole mesh the kernel covers (swe2d_plan.hip: step_plan; SWE2D_OPT_FUSED_STAGES forces or forbids it).
 //
 // A stage launch streams the state: per triangle and step 72 B read + 72 B written in stage 1, 72 + 72 B read + 72 B written in
 // stage 2.  U(1) is read by stage 2 and by nothing else (rungekutta.py:ERKGenericShuOsher, stage 3 takes

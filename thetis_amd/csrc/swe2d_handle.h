@@ -138,7 +138,7 @@ struct Handle {
     int2 *fuse_tile = nullptr;
     int *fuse_inner = nullptr;
     int fuse_n_tiles = 0;
-    int fuse_state = 0;                                 // -1: the numbering gives poor tiles, -2: first use inside a stream capture: stage launches
+    int fuse_state = 0;                                 // -1: the numbering gives poor tiles (stage launches until an option or the order changes)
     long long fuse_ring_cells = 0;
     // ... the stage pair on quadrilaterals (swe_fuse12_quad_kernel)
     int4 *fuseq_tile = nullptr;
@@ -346,16 +346,29 @@ inline bool conn_pays(const Handle *h, int n_cells_of_launch, bool arithmetic_bo
     const int o = h->opt[SWE2D_OPT_COMPACT_IDX];
     return h->idxc && o != 0 && (o == 2 || (n_cells_of_launch >= 250000 && !arithmetic_bound));
 }
-bool fuse12_covers(const Handle *h);
 int fuse12_build(Handle *h);
 int launch_fuse12(Handle *h, int cell_end);
-bool fuse123_wanted(const Handle *h);
 int fuse123_build(Handle *h);
 int launch_fuse123(Handle *h, int cell_end);
 int capture_parity_check(Handle *h);                    // SWE2D_ERR_UNSUPPORTED once after a capture that swapped the state buffers an odd number of times
 bool stream_capturing(Handle *h, unsigned long long *id = nullptr);   // is the handle's stream capturing (and which capture)?
 void stage_written(Handle *h, bool s0, bool s1);        // a launch left U(1) / U(2) in buffers B / C (none of it inside a capture)
-int step_swe(Handle *h);                               // one SSPRK33 step of the shallow-water state on the whole mesh: fused pair + stage 3, or stage launches
+inline void stage_invalidate(Handle *h) { h->stage_valid[0] = h->stage_valid[1] = false; }   // neither buffer holds a stage solution of the current state
+inline void swap_state_buffers(Handle *h) { std::swap(h->state[0], h->state[1]); stage_invalidate(h); }   // A and B change places: B holds an older state, no stage solution
+// ---- how a step is launched (swe2d_plan.hip)
+enum StepPath : unsigned { kStages = 0, kPair = 1, kTriple = 2, kFlow = 4 };   // three stage launches | fused pair + stage 3 | three-stage kernel | dataflow kernel
+// who asks: swe2d_advance on a whole mesh | a whole-mesh step without the dataflow kernel (swe2d_advance_coupled, swe2d_advance_timed per
+// launch) | a partition's stage pair (swe2d_solve_stage_pair_cells) | a partition's whole step (swe2d_fused_step_info)
+enum StepCaller { kAdvance, kWholeStep, kPartitionPair, kPartitionStep };
+unsigned step_kernels(const Handle *h);                 // the kernels (StepPath bits) that cover the handle's configuration, whatever its size
+StepPath step_plan(Handle *h, StepCaller who, StepPath at_most = kFlow);        // the path the caller takes by size and options
+int step_ready(Handle *h, StepCaller who, StepPath at_most, StepPath *path);    // ... with its tile tables built, or the next path without
+int whole_step_path(Handle *h, StepCaller who, StepPath *path);                 // ... of a whole-mesh step that may be inside a stream capture
+inline int launches_per_step(StepPath p) { return p == kTriple ? 1 : (p == kPair ? 2 : 3); }
+int step_launch(Handle *h, StepPath path, int i);       // launch i of a whole-mesh step by kStages / kPair / kTriple
+int step_swe(Handle *h, StepCaller who, int n_steps);   // n_steps SSPRK33 steps of the shallow-water state on the whole mesh (kAdvance / kWholeStep)
+bool fuse12_tiles_pay(const Handle *h, int n_tiles);    // are the stage pair's tiles worth it (else fuse_state = -1)?
+bool flow_fits(Handle *h);                              // every 64-cell block of the handle resident at once
 void fill_stage_args(Handle *h, SweStageArgs &a, int in, int u0, int out, double a0, double a1, double beta, int c0, int c1);
 int launch_stage(Handle *h, int in, int u0, int out, double a0, double a1, double beta, int c0, int c1);
 int stage_on_range(Handle *h, int i_stage, int c0, int c1);
@@ -365,7 +378,6 @@ int scatter_facet_values(Handle *h, double *planes, int n, const int32_t *cells,
 int upload_vertex_coefficient(Handle *h, const double *vertex_values, double **dev);
 // ---- dataflow stage loop (swe2d_api_flow.hip)
 int flow_build(Handle *h, const int32_t *order);
-bool flow_kernel_covers(const Handle *h);
 int flow_capacity(Handle *h);
 int flow_build_exchange(Handle *h);
 int launch_flow(Handle *h, int n_stages, const int32_t *cell_end, int n_cycles = 0);

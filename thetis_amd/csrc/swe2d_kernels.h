@@ -729,7 +729,7 @@ __device__ __forceinline__ double swe_farm_drag_quad(const SweStageArgs &p, unsi
 // Optional cell-local terms (SRC kernel variant): Coriolis, linear / quadratic / Manning drag, atmospheric pressure
 // gradient, momentum and volume sources.  b-vectors are the assembled integrals (before the mass inverse).
 // FARMS: the instance also carries the tidal turbine farms (the stage kernels; the fused and the dataflow kernels, which have no
-// registers to spare, do not - handles with farms never reach them, see fuse_applies / flow_kernel_covers).
+// registers to spare, do not - handles with farms never reach them, see step_kernels, swe2d_plan.hip).
 template <bool FARMS = false>
 __device__ __forceinline__ void swe_source_terms(const SweStageArgs &p, int k, size_t S, double twoA, const double u[3],
                                                  const double v[3], const double H[3], const double gxs[3],
