@@ -249,6 +249,15 @@ fuse3_kernel_t pick_fuse3_kernel(bool nl, bool lf, bool src) { return src ? pick
 // position the caller marked as the start of a tile (swe2d_fused_set_triple_tiles: patches of 11 x 8 quads = 176 triangles + 38 + 42
 // fill the 256 lanes, where 147 consecutive cells of the 16 x 6 numbering leave ragged patches with rings of 52 + 57).
 // Allocations and copies: not inside a stream capture - there it builds nothing (fuse3_tile stays null) and the caller goes without.
+//
+// Lanes: role r of a tile ([interior | ring 1 | ring 2 | padding]) sits on the physical lane (r + 64*rot) & 255.  The wave that holds the
+// last 64 roles runs two stage bodies, the other three run three; which wave that is follows from rot, and rot from the tile number by
+// SWE_FUSE3_ROT - a host-side policy, the kernel reads it from counts[tile].y >> 16.  Not tile & 3: the XCD-chunked block map and the
+// dealing of workgroups over the compute units of an XCD can hand one compute unit tiles of a single residue.  The top two bits of
+// tile x 2^32/phi instead: every arithmetic progression of tile numbers meets the four values equally often.
+#ifndef SWE_FUSE3_ROT
+#define SWE_FUSE3_ROT(tile) ((int)(((unsigned)(tile)*0x9E3779B1u) >> 30))
+#endif
 int fuse123_build(Handle *h)
 {
     if (h->fuse3_tile || stream_capturing(h)) return SWE2D_OK;
@@ -304,7 +313,9 @@ int fuse123_build(Handle *h)
             for (int c : touched) if (state[c] == want) cells.push_back(c);
         const int ni = (int)inner.size(), nm = ni + count[2], nt = (int)cells.size();
         if (nt != count[1] + count[2] + count[3] || ni != count[1] || nt > SWE_FUSE_WG) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stages: tile bookkeeping");
-        for (int l = 0; l < nt; l++) lane_of[cells[l]] = l;
+        const int rot = SWE_FUSE3_ROT((int)cnt.size()) & 3;
+        auto phys = [rot](int role) { return (role + 64*rot) & (SWE_FUSE_WG - 1); };
+        for (int l = 0; l < nt; l++) lane_of[cells[l]] = phys(l);
         const size_t base = tl.size();
         tl.resize(base + SWE_FUSE_WG, int2{-1, 0});
         int n_out = 0;
@@ -314,7 +325,7 @@ int fuse123_build(Handle *h)
             for (int f = 0; f < 3; f++) {
                 const int code = nbr[(size_t)f*S + c];
                 unsigned field;
-                if (code < 0) field = (unsigned)l;                                   // boundary facet: the cell itself
+                if (code < 0) field = (unsigned)phys(l);                             // boundary facet: the cell itself
                 else if (state[code >> 2] != 0) field = (unsigned)lane_of[code >> 2];
                 else {
                     if (l < nm || n_out >= SWE_FUSE3_MAX_OUT) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stages: ring bookkeeping");
@@ -322,9 +333,9 @@ int fuse123_build(Handle *h)
                 }
                 w |= field << (SWE_FUSE_FBITS*f);
             }
-            tl[base + l] = int2{c, (int)w};
+            tl[base + phys(l)] = int2{c, (int)w};
         }
-        cnt.push_back(int2{ni, nm});
+        cnt.push_back(int2{ni, nm | (rot << 16)});
         r1_total += count[2]; r2_total += count[3];
         for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
     }

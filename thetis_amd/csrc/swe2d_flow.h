@@ -284,11 +284,19 @@ __device__ __forceinline__ void swe_flow_rhs_cell(const SweStageArgs &p, const d
 // (XG, PLANE: where the staging area starts and how long a plane of the block's own values is - the fused stage pair of swe2d_fuse.h
 //  has 256-lane planes)
 // (NLDS: the size of the array `lds` points into - what the -DSWE_RANGE_CHECK build tests every index against)
-template <bool NONLIN, bool LF, bool SRC, int NTR, bool WD = false, int XG = SWE_FLOW_XG, int PLANE = SWE_BLOCK, int NLDS = SWE_FLOW_LDS_DOUBLES>
+// (GEOM: what becomes of the facet lengths, pure functions of the mesh - SWE_GEOM_COMPUTE: evaluated here, every caller but the
+//  three-stage kernel of swe2d_fuse.h; SWE_GEOM_KEEP: evaluated here and left in the lane's LDS record, geo[f*PLANE] = Lf and
+//  geo[(3 + f)*PLANE] = 1/Lf of facet f; SWE_GEOM_STORED: taken from the record a SWE_GEOM_KEEP call filled - the values that
+//  instruction sequence gave, so the same bits.  swe_flow_finish: geo[6*PLANE] = 1/twoA in the same way)
+#define SWE_GEOM_COMPUTE 0
+#define SWE_GEOM_KEEP 1
+#define SWE_GEOM_STORED 2
+template <bool NONLIN, bool LF, bool SRC, int NTR, bool WD = false, int XG = SWE_FLOW_XG, int PLANE = SWE_BLOCK, int NLDS = SWE_FLOW_LDS_DOUBLES,
+          int GEOM = SWE_GEOM_COMPUTE>
 __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k, const double u[3], const double v[3], const double e[3],
                                                     const double h[3], const double *lds, const unsigned tr[3][NTR], int bmarkers,
                                                     const double nx[3], const double ny[3], double twoA, double bu[3], double bv[3],
-                                                    double be[3], const double *Dn = nullptr, const double *al = nullptr)
+                                                    double be[3], const double *Dn = nullptr, const double *al = nullptr, double *geo = nullptr)
 {
 #pragma clang fp contract(off)
     const double g = p.g;
@@ -306,7 +314,9 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
         const double enb = lds[SWE_LDSI(ab2, NLDS)], ena = lds[SWE_LDSI(aa2, NLDS)];
         const double nxs = nx[f], nys = ny[f];
         double Lf, rLf;
-        swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), Lf, rLf);
+        if constexpr (GEOM == SWE_GEOM_STORED) { Lf = geo[f*PLANE]; rLf = geo[(3 + f)*PLANE]; }
+        else swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), Lf, rLf);
+        if constexpr (GEOM == SWE_GEOM_KEEP) { geo[f*PLANE] = Lf; geo[(3 + f)*PLANE] = rLf; }
         double Fau, Fbu, Fav, Fbv, Fae, Fbe;
         if constexpr (WD) {
             // the neighbour's traces carry its nodal depth D; its elevation by the closed form (bathymetry and alpha are continuous)
@@ -335,15 +345,21 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
 
 // mass inverse, Shu-Osher combine and the boundary facets of the cell (the BINL pass of swe_stage_kernel)
 // (WALLFAST: the closed-wall path of swe_boundary_facet; not in the variants with source terms - no registers to spare, 68 B of scratch)
-template <bool NONLIN, bool LF, bool WALLFAST, bool WD = false>
+template <bool NONLIN, bool LF, bool WALLFAST, bool WD = false, int GEOM = SWE_GEOM_COMPUTE, int PLANE = SWE_BLOCK>
 __device__ __forceinline__ void swe_flow_finish(const SweStageArgs &p, int k, double beta, const double u[3], const double v[3],
                                                 const double e[3], const double h[3], const double nx[3], const double ny[3],
                                                 double twoA, int bmarkers, int bkind1, const double bu[3], const double bv[3], const double be[3],
                                                 const double wu[3], const double wv[3], const double we[3], double ou[3],
-                                                double ov[3], double oe[3], const double *Dn = nullptr, const double *al = nullptr)
+                                                double ov[3], double oe[3], const double *Dn = nullptr, const double *al = nullptr,
+                                                double *geo = nullptr)
 {
 #pragma clang fp contract(off)
-    const double s = 6.0*p.dt*beta*swe_rcp(twoA);
+    const double dtb6 = 6.0*p.dt*beta;
+    double rA;
+    if constexpr (GEOM == SWE_GEOM_STORED) rA = geo[6*PLANE];
+    else rA = swe_rcp(twoA);
+    if constexpr (GEOM == SWE_GEOM_KEEP) geo[6*PLANE] = rA;
+    const double s = dtb6*rA;
     const double su = bu[0] + bu[1] + bu[2], sv = bv[0] + bv[1] + bv[2], se = be[0] + be[1] + be[2];
 #pragma unroll
     for (int i = 0; i < 3; i++) {

@@ -194,11 +194,30 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 // LDS: P0 [9][256] = U(0) (traces of stage 1; every lane's own U(0) for the Shu-Osher weights of stages 2 and 3), P1 [9][256] = the
 // running stage values (U(1), then U(2)), then the staging area of the traces from outside the tile: 36.9 KB + 6 x 8 B per slot.
 // Same arithmetic, same order as the stage launches: the same bits (tests/test_gpu_parity.py::test_fused_stage_triple...).
-#define SWE_FUSE3_XG (18*SWE_FUSE_WG)                   // the staging area follows P0 and P1
+//
+// Roles and lanes (round 10).  The ROLES of a tile are numbered [interior | ring 1 | ring 2 | padding]; role r sits on the physical
+// lane (r + 64*rot) & 255, rot in 0..3 per tile, kept in counts[tile].y >> 16 (fuse123_build: SWE_FUSE3_ROT).  Stage 2 runs the roles
+// below n_mid (~214 on the bench mesh), stage 3 those below n_inner (~176): the wave that holds the last 64 roles executes two stage
+// bodies where the others execute three, and with rot = 0 everywhere that is wave 3 of every workgroup.  Everything the table says
+// about lanes - the neighbour-lane fields, hence the LDS planes - is physical; only the two activity tests look at the role.
+//
+// The cell constants (round 10).  What a stage body derives from the mesh alone - the three facet lengths, their reciprocals and
+// 1/twoA, 44 of its ~511 FP64 instructions - stage 1 leaves in LDS as it forms them (SWE_GEOM_KEEP of swe2d_flow.h), plane by plane
+// ([7][256] by physical lane behind P1: conflict-free), and stages 2 and 3 read them where they are used (SWE_GEOM_STORED) instead of
+// evaluating them again: no register lives longer for it.  The room is the staging area's, which moves INTO P1: nobody reads or writes
+// P1 before stage 1's results go there, and those now wait for one more barrier (every lane has read its traces of U(0)).
+// 25 planes of 256 doubles = 51.2 KB, three workgroups per CU as before (47.6 KB).
 #ifndef SWE_FUSE3_MAX_OUT
 #define SWE_FUSE3_MAX_OUT 224                           // staging slots (a ring-2 cell has at most two facets towards the outside)
 #endif
-#define SWE_FUSE3_LDS (SWE_FUSE3_XG + 6*SWE_FUSE3_MAX_OUT)
+#ifndef SWE_FUSE3_GEOM
+#define SWE_FUSE3_GEOM 1                                // 0: the layout and the arithmetic of round 6 - staging area behind P1, no records (A/B builds)
+#endif
+#define SWE_FUSE3_NGEO 7                                // Lf[3], 1/Lf[3], 1/twoA
+#define SWE_FUSE3_GEO (18*SWE_FUSE_WG)                  // the records follow P0 and P1
+#define SWE_FUSE3_XG (SWE_FUSE3_GEOM ? 9*SWE_FUSE_WG : 18*SWE_FUSE_WG)       // the staging area: P1 while stage 1 runs
+#define SWE_FUSE3_LDS (SWE_FUSE3_GEOM ? SWE_FUSE3_GEO + SWE_FUSE3_NGEO*SWE_FUSE_WG : SWE_FUSE3_XG + 6*SWE_FUSE3_MAX_OUT)
+static_assert(6*SWE_FUSE3_MAX_OUT <= 9*SWE_FUSE_WG, "the staging area must fit P1");
 #ifndef SWE_FUSE3_SRC_MIN_WG
 #define SWE_FUSE3_SRC_MIN_WG 2                          // the source-term instances need 187-199 VGPRs: two workgroups per CU (at three: 80-132 B of scratch per lane)
 #endif
@@ -206,7 +225,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 struct SweFuse3Args {
     SweStageArgs st;          // uin = U(0) (state buffer A); geometry, connectivity, boundary tables; dt, g, sigma_lf
     const int2 *tile;         // [n_tiles][256]: as SweFuseArgs::tile (lane of the neighbour in the tile, or bit 9 + staging slot)
-    const int2 *counts;       // [n_tiles]: {n_inner, n_mid}
+    const int2 *counts;       // [n_tiles]: {n_inner, n_mid | rot << 16}: roles 0 .. n_inner-1 interior, .. n_mid-1 ring 1; role r on lane (r + 64 rot) & 255
     int n_tiles;
     int cell_end;             // stage 3 (the only one that leaves the chip) on cells [0, cell_end): a partition's last stage range
     double a0[3], a1[3], beta[3];   // Shu-Osher weights per stage (swe2d_ssprk33_coefficients)
@@ -226,9 +245,13 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     const bool real = tl.x >= 0;
     const int k = real ? tl.x : 0;
     const int2 cnt = q.counts[tile];
+    const int n_inner = cnt.x, n_mid = cnt.y & 0xffff, rot64 = (cnt.y >> 16) << 6;
     const size_t S = p.stride;
     const unsigned S8 = (unsigned)S*8u, k8 = (unsigned)k*8u;
     double *const P1 = lds + 9*SWE_FUSE_WG;
+#ifdef SWE_WAVE_TIMING
+    int wt_bodies = __any(real) ? 1 : 0;                   // profiling build only (tools/fuse3timing.py): stage bodies this wave executes
+#endif
 
     int bmarkers = 0, bkind1 = 0;
     unsigned tr[3][1];
@@ -297,18 +320,25 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         }
     }
     __syncthreads();
-    // ---- stage 1 on every cell of the tile: U(1) = U(0) + beta1 dt M^-1 R(U(0)), into P1 (nobody reads P1 yet: no barrier in front)
+    // ---- stage 1 on every cell of the tile: U(1) = U(0) + beta1 dt M^-1 R(U(0)), into P1
+    constexpr int GEOM1 = SWE_FUSE3_GEOM ? SWE_GEOM_KEEP : SWE_GEOM_COMPUTE, GEOM23 = SWE_FUSE3_GEOM ? SWE_GEOM_STORED : SWE_GEOM_COMPUTE;
     double twoA = 0.0;
+    double *const G = lds + SWE_FUSE3_GEO + lane;          // the lane's record of cell constants: G[j*256]
     if (real) {
         twoA = fma(nx[0], ny[1], -(ny[0]*nx[1]));
         double bu[3], bv[3], be[3], wu[3], wv[3], we[3], ou[3], ov[3], oe[3];
         swe_flow_rhs_cell<NONLIN>(p, u, v, e, h, nx, ny, bu, bv, be);
-        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be);
+        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+                                                                                                     nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
-        swe_flow_finish<NONLIN, LF, true>(p, k, q.beta[0], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe);
+        swe_flow_finish<NONLIN, LF, true, false, GEOM1, SWE_FUSE_WG>(p, k, q.beta[0], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe,
+                                                        nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { u[i] = ou[i]; v[i] = ov[i]; e[i] = oe[i]; }
+    }
+    if (SWE_FUSE3_GEOM) __syncthreads();                   // every lane has read its traces of U(0): the staging area is P1 again
+    if (real) {
 #pragma unroll
         for (int i = 0; i < 3; i++) { P1[i*SWE_FUSE_WG + lane] = u[i]; P1[(3 + i)*SWE_FUSE_WG + lane] = v[i]; P1[(6 + i)*SWE_FUSE_WG + lane] = e[i]; }
     }
@@ -317,7 +347,11 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     //      U(0) for the weights from P0
 #pragma unroll 1
     for (int s = 1; s < 3; s++) {
-        const bool act = lane < (s == 1 ? cnt.y : cnt.x) && (s == 1 || k < q.cell_end);
+        const int role = (lane - rot64) & (SWE_FUSE_WG - 1);
+        const bool act = role < (s == 1 ? n_mid : n_inner) && (s == 1 || k < q.cell_end);
+#ifdef SWE_WAVE_TIMING
+        wt_bodies += __any(act) ? 1 : 0;
+#endif
         double ou[3], ov[3], oe[3];
         if (act) {
             // opaque to the optimiser (as in swe_flow_kernel): what the previous stage derived from the geometry would otherwise stay
@@ -326,10 +360,12 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             for (int i = 0; i < 3; i++) asm volatile("" : "+v"(nx[i]), "+v"(ny[i]), "+v"(h[i]));
 #pragma unroll
             for (int f = 0; f < 3; f++) asm volatile("" : "+v"(tr[f][0]));
-            asm volatile("" : "+v"(bmarkers), "+v"(twoA));
+            asm volatile("" : "+v"(bmarkers));
+            if (SRC || !SWE_FUSE3_GEOM) asm volatile("" : "+v"(twoA));     // (else nothing reads it after stage 1)
             double bu[3], bv[3], be[3], wu[3], wv[3], we[3];
             swe_flow_rhs_cell<NONLIN>(p, u, v, e, h, nx, ny, bu, bv, be);
-            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be);
+            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+                                                                                                          nullptr, nullptr, G);
             const double a0 = q.a0[s], a1 = q.a1[s];
 #pragma unroll
             for (int i = 0; i < 3; i++) {
@@ -337,7 +373,8 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
                 wv[i] = fma(a0, lds[(3 + i)*SWE_FUSE_WG + lane], a1*v[i]);
                 we[i] = fma(a0, lds[(6 + i)*SWE_FUSE_WG + lane], a1*e[i]);
             }
-            swe_flow_finish<NONLIN, LF, true>(p, k, q.beta[s], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe);
+            swe_flow_finish<NONLIN, LF, true, false, GEOM23, SWE_FUSE_WG>(p, k, q.beta[s], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe,
+                                                                          nullptr, nullptr, G);
         }
         if (s == 1) {
             __syncthreads();                               // every lane has read its traces of U(1)
@@ -358,6 +395,17 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             }
         }
     }
+#ifdef SWE_WAVE_TIMING
+    // where did the wave run, and how much of the tile's work did it do?  HW_ID | XCC_ID << 32 | stage bodies << 40 | 1 << 44, per
+    // wave of the launch: swe_wave_ts read as one array of 6*SWE_WT_MAX words, word 4*blockIdx.x + wave
+    if ((lane & 63) == 0 && 4*blockIdx.x + (lane >> 6) < 6*SWE_WT_MAX) {
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        (&swe_wave_ts[0][0])[4*blockIdx.x + (lane >> 6)] = (unsigned long long)hw | ((unsigned long long)(xcc & 0xf) << 32)
+                                                           | ((unsigned long long)wt_bodies << 40) | (1ull << 44);
+    }
+#endif
 }
 
 // (Round 6, measured and removed: the three stages of a TRACER step in one launch on these two-ring tiles - the tracer in LDS between
