@@ -5,102 +5,12 @@ Deterministic seeds; the single-option tests elsewhere localise a failure, this 
 import numpy as np
 import pytest
 
+from fuzz_cases import random_config as _random_config
 from helpers import channel_case, make_oracle, make_oracle_generic, quad_case, rel_linf
 from thetis_amd import _lib
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-12
-
-
-def _random_config(rng, mesh, quad):
-    n, k = mesh.num_cells, mesh.cells.shape[1]
-    x, y = mesh.vertex_xy.T
-    o, dev_ops = {}, []                       # oracle kwargs, device calls (name, args)
-    nonlin = bool(rng.integers(0, 2))
-    wd = nonlin and rng.random() < 0.25
-    o['use_nonlinear_equations'] = nonlin
-    o['use_lax_friedrichs_velocity'] = bool(rng.integers(0, 2))
-    o['lax_friedrichs_velocity_scaling_factor'] = float(rng.choice([1.0, 0.6]))
-    if wd:
-        o.update(use_wetting_and_drying=True, wetting_and_drying_alpha=0.5 + 0.3*rng.random(), wd_mode='nodal')
-        dev_ops.append(('set_wetting_and_drying', (o['wetting_and_drying_alpha'],)))
-    if rng.random() < 0.5:
-        cor = 1e-4*(1 + y/(abs(y).max() + 1.0))
-        o['coriolis'] = cor
-        dev_ops.append(('set_field', (_lib.FIELD_CORIOLIS, cor[mesh.cells])))
-    if rng.random() < 0.4:
-        pa = 1e5 + 300*np.sin(x/2e4)
-        o['atmospheric_pressure'] = pa
-        dev_ops.append(('set_field', (_lib.FIELD_ATMOSPHERIC_PRESSURE, pa[mesh.cells])))
-    if rng.random() < 0.4:
-        ms = 1e-3*rng.normal(size=(n, k, 2))
-        o['momentum_source'] = ms
-        dev_ops.append(('set_field', (_lib.FIELD_MOMENTUM_SOURCE, ms)))
-    if rng.random() < 0.4:
-        vs = 1e-3*rng.normal(size=(n, k))
-        o['volume_source'] = vs
-        dev_ops.append(('set_field', (_lib.FIELD_VOLUME_SOURCE, vs)))
-    if rng.random() < 0.3:
-        ws = 0.1*rng.normal(size=(n, k, 2))
-        o['wind_stress'] = ws
-        dev_ops.append(('set_field', (_lib.FIELD_WIND_STRESS, ws)))
-    lin = rng.random()
-    if lin < 0.25:
-        o['linear_drag_coefficient'] = 1e-3
-        dev_ops.append(('set_scalar', (_lib.SCALAR_LINEAR_DRAG, 1e-3)))
-    elif lin < 0.45:
-        c = 1e-3*(1 + x/(abs(x).max() + 1.0))
-        o['linear_drag_coefficient'] = c
-        dev_ops.append(('set_field', (_lib.FIELD_LINEAR_DRAG, c[mesh.cells])))
-    drag = rng.integers(0, 7)
-    field = 1.0 + 0.5*x/(abs(x).max() + 1.0)
-    if drag == 1:
-        o['quadratic_drag_coefficient'] = 0.0025
-        dev_ops.append(('set_scalar', (_lib.SCALAR_QUADRATIC_DRAG, 0.0025)))
-    elif drag == 2:
-        o['manning_drag_coefficient'] = 0.02
-        dev_ops.append(('set_scalar', (_lib.SCALAR_MANNING_DRAG, 0.02)))
-    elif drag == 3:
-        o['nikuradse_bed_roughness'] = 0.05
-        dev_ops.append(('set_scalar', (_lib.SCALAR_NIKURADSE, 0.05)))
-    elif drag == 4:
-        o['manning_drag_coefficient'] = 0.02*field
-        dev_ops.append(('set_field', (_lib.FIELD_MANNING_DRAG, (0.02*field)[mesh.cells])))
-    elif drag == 5:
-        o['quadratic_drag_coefficient'] = 0.0025*field
-        dev_ops.append(('set_field', (_lib.FIELD_QUADRATIC_DRAG, (0.0025*field)[mesh.cells])))
-    if drag and rng.random() < 0.5:
-        o['norm_smoother'] = 0.05
-        dev_ops.append(('set_scalar', (_lib.SCALAR_NORM_SMOOTHER, 0.05)))
-    visc = None
-    if rng.random() < 0.4:
-        nu = 30.0 if rng.random() < 0.5 else 20.0 + 20.0*rng.uniform(size=mesh.num_vertices)
-        visc = dict(sipg_factor=float(rng.choice([1.0, 2.0])), use_grad_div_viscosity_term=bool(rng.integers(0, 2)),
-                    use_grad_depth_viscosity_term=bool(rng.integers(0, 2)))
-        o.update(horizontal_viscosity=nu, **visc)
-        dev_ops.append(('set_viscosity', (nu,), visc))
-    # boundaries
-    bcs = {}
-    kinds = [None, {'elev': 1}, {'uv': 1}, {'un': 1}, {'flux': 1}, {'elev': 1, 'uv': 1}, {'elev': 1, 'un': 1}, {'elev': 1, 'flux': 1}]
-    for marker in (1, 2, 3, 4):
-        kind = kinds[int(rng.integers(0, len(kinds)))]
-        funcs = {}
-        for key in (kind or {}):
-            as_field = rng.random() < 0.4
-            if key == 'elev':
-                funcs[key] = 0.1*rng.normal(size=(n, k)) if as_field else 0.1*rng.normal()
-            elif key == 'uv':
-                funcs[key] = 0.2*rng.normal(size=(n, k, 2)) if as_field else tuple(0.2*rng.normal(size=2))
-            elif key == 'un':
-                funcs[key] = 0.2*rng.normal(size=(n, k)) if as_field else 0.2*rng.normal()
-            else:
-                funcs[key] = 2e4*rng.normal(size=(n, k)) if as_field else 2e4*rng.normal()
-        if rng.random() < 0.2:
-            funcs['drag'] = 0.01
-        if funcs:
-            bcs[marker] = funcs
-    o['bnd_conditions'] = bcs
-    return o, dev_ops, bcs, wd
 
 
 @pytest.mark.parametrize('seed', range(192))
