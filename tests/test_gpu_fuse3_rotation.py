@@ -1,15 +1,15 @@
 """csrc/swe2d_fuse.h, swe_fuse123_kernel with rotated tiles and stored cell constants (round 10).
 
 A tile's roles [interior | ring 1 | ring 2 | padding] sit on the physical lanes (role + 64*rot) & 255, rot per tile from the tile
-number (csrc/swe2d_api_fuse.hip: SWE_FUSE3_ROT); stage 1 leaves the facet lengths, their reciprocals and 1/twoA in LDS and stages 2
+number (csrc/swe2d_tiles.h: SWE_FUSE3_ROT); stage 1 leaves the facet lengths, their reciprocals and 1/twoA in LDS and stages 2
 and 3 read them back.  Neither may change a bit: the yardstick is the one of tests/test_gpu_parity.py::test_fused_stage_triple... -
 the three-stage launch against three stage launches, ``==`` on the float64 arrays after 3 steps, the path switched through
 SWE2D_OPT_FUSED_STAGES.
 
 The tile table itself (each cell interior in exactly one tile, neighbour-lane fields pointing at physical lanes, n_inner <= n_mid <=
-256) cannot be read back through the ABI of include/swe2d.h, and a second builder in Python would test itself: the table is covered
-by the bitwise comparisons alone - a neighbour field that pointed at the wrong lane, a cell updated twice or not at all, or a count
-that cut a ring short would each change the state the launches leave."""
+256) cannot be read back through the ABI of include/swe2d.h: tests/test_tile_tables.py checks it on the host, here it is covered by
+the bitwise comparisons - a neighbour field that pointed at the wrong lane, a cell updated twice or not at all, or a count that cut
+a ring short would each change the state the launches leave."""
 import os
 
 import numpy as np
@@ -23,7 +23,7 @@ COAST = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'coas
 
 
 def _rot(tile):
-    """csrc/swe2d_api_fuse.hip SWE_FUSE3_ROT: the top two bits of tile x 2^32/phi"""
+    """csrc/swe2d_tiles.h SWE_FUSE3_ROT: the top two bits of tile x 2^32/phi"""
     return ((tile*0x9E3779B1) & 0xffffffff) >> 30
 
 

@@ -264,8 +264,7 @@ int swe2d_fused_pair_info(swe2d_handle *hh, int32_t out[4])
     if (path != kFlow) { if (int rc = step_ready(h, who, kPair, &path)) return rc; }
     if (path != kPair) return SWE2D_OK;
     out[0] = 1;
-    if (h->npc == 4) { out[1] = h->fuseq_n_tiles; out[2] = (int32_t)h->fuseq_ring_cells; }
-    else { out[1] = h->fuse_n_tiles; out[2] = (int32_t)h->fuse_ring_cells; }
+    out[1] = pair_tiles(h).n_tiles; out[2] = (int32_t)pair_tiles(h).ring[0];
     return SWE2D_OK;
 }
 
@@ -551,8 +550,9 @@ void swe2d_destroy(swe2d_handle *hh)
     }
     void *ptrs[] = {h->nbr, h->cv, h->vx, h->vy, h->vh, h->stage_uv, h->stage_eta, h->partial, h->diag_acc, h->send_cells, h->recv_cells,
                     h->lim_v2c_off, h->lim_v2c_cell, h->lim_vbf_off, h->lim_vbf_facet, h->lim_tv, h->lim_mean,
-                    h->lim_qmin, h->lim_qmax, h->valpha, h->snapshot[0].data, h->snapshot[1].data, h->bc_field[0], h->bc_field[1], h->bc_field[2], h->bc_field[3], h->nu_v, h->idx4, h->idx2, h->idxc, h->fuse_tile, h->fuse_inner, h->fuse3_tile, h->fuse3_cnt, h->fuseq_tile, h->fuseq_inner, h->opp4, h->bnd_cells, h->flow_flag, h->flow_status, h->flow_xo4, h->flow_xo2, h->flow_ex, h->flow_xblk, h->flow_xsrc, h->flow_cell, h->flow_xsend, h->flow_xrecv, h->flow_xtick};
+                    h->lim_qmin, h->lim_qmax, h->valpha, h->snapshot[0].data, h->snapshot[1].data, h->bc_field[0], h->bc_field[1], h->bc_field[2], h->bc_field[3], h->nu_v, h->idx4, h->idx2, h->idxc, h->opp4, h->bnd_cells, h->flow_flag, h->flow_status, h->flow_xo4, h->flow_xo2, h->flow_ex, h->flow_xblk, h->flow_xsrc, h->flow_cell, h->flow_xsend, h->flow_xrecv, h->flow_xtick};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (TileSet *ts : {&h->fuse, &h->fuseq, &h->fuse3}) free_tiles(*ts);
     for (auto &fl : h->facet_lists) if (fl.dev) (void)hipFree(fl.dev);
     for (void *m : h->p2p.opened) (void)hipIpcCloseMemHandle(m);
     if (h->p2p.zone) (void)hipFree(h->p2p.zone);

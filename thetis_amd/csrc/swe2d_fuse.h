@@ -196,7 +196,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 // Same arithmetic, same order as the stage launches: the same bits (tests/test_gpu_parity.py::test_fused_stage_triple...).
 //
 // Roles and lanes (round 10).  The ROLES of a tile are numbered [interior | ring 1 | ring 2 | padding]; role r sits on the physical
-// lane (r + 64*rot) & 255, rot in 0..3 per tile, kept in counts[tile].y >> 16 (fuse123_build: SWE_FUSE3_ROT).  Stage 2 runs the roles
+// lane (r + 64*rot) & 255, rot in 0..3 per tile, kept in counts[tile].y >> 16 (swe2d_tiles.h: SWE_FUSE3_ROT).  Stage 2 runs the roles
 // below n_mid (~214 on the bench mesh), stage 3 those below n_inner (~176): the wave that holds the last 64 roles executes two stage
 // bodies where the others execute three, and with rot = 0 everywhere that is wave 3 of every workgroup.  Everything the table says
 // about lanes - the neighbour-lane fields, hence the LDS planes - is physical; only the two activity tests look at the role.

@@ -97,6 +97,14 @@ extern const double kBeta[3], kAlpha0[3], kAlphaIn[3];
 
 extern std::atomic<unsigned long long> g_next_uid;
 
+// the tile tables of one fused kernel on the device (swe2d_api_fuse.hip: upload_tiles / free_tiles); tile == null: not built
+struct TileSet {
+    void *tile = nullptr;                               // [n_tiles][256] records: int2, quadrilaterals int4 (SweFuseArgs / SweFuseQuadArgs / SweFuse3Args)
+    int *counts = nullptr;                              // [n_tiles] n_inner; two-ring tiles: int2 {n_inner, n_mid | rot << 16}
+    int n_tiles = 0;
+    long long ring[2] = {0, 0};                         // cells of ring 1 / ring 2 over all tiles
+};
+
 struct Handle {
     unsigned long long uid = g_next_uid.fetch_add(1ull);   // never reused (a freed handle's address may be)
     int device = 0;
@@ -134,21 +142,11 @@ struct Handle {
     int4 *idx4 = nullptr;                               // packed triangle connectivity (stage kernel), see SweStageArgs
     int2 *idx2 = nullptr;
     int4 *idxc = nullptr;                               // ... in 16 B (swe_conn_pack), what the stage kernels read (SWE2D_OPT_COMPACT_IDX)
-    // stages 1 + 2 of a step in one launch by overlapped tiles (swe2d_fuse.h; SWE2D_OPT_FUSED_STAGES): tile tables, built at first use
-    int2 *fuse_tile = nullptr;
-    int *fuse_inner = nullptr;
-    int fuse_n_tiles = 0;
+    // tile tables of the fused stage kernels (swe2d_fuse.h; SWE2D_OPT_FUSED_STAGES), built at first use (swe2d_tiles.h): the stage pair
+    // on triangles (swe_fuse12_kernel), on quadrilaterals (swe_fuse12_quad_kernel), all three stages with two rings per tile
+    // (swe_fuse123_kernel)
+    TileSet fuse, fuseq, fuse3;
     int fuse_state = 0;                                 // -1: the numbering gives poor tiles (stage launches until an option or the order changes)
-    long long fuse_ring_cells = 0;
-    // ... the stage pair on quadrilaterals (swe_fuse12_quad_kernel)
-    int4 *fuseq_tile = nullptr;
-    int *fuseq_inner = nullptr;
-    int fuseq_n_tiles = 0;
-    long long fuseq_ring_cells = 0;
-    // ... all three stages in one launch, two rings per tile (SWE2D_OPT_FUSED_STAGES = 3): tile tables, built at first use
-    int2 *fuse3_tile = nullptr, *fuse3_cnt = nullptr;
-    int fuse3_n_tiles = 0;
-    long long fuse3_ring1 = 0, fuse3_ring2 = 0;
     std::vector<int> fuse_order;                        // cells in the order the tiles are cut from (swe2d_fused_set_order); empty: the numbering
     std::vector<int> fuse3_order;                       // the same for the two-ring tiles alone (swe2d_fused_set_triple_tiles); empty: fuse_order
     std::vector<unsigned char> fuse3_start;             // [n_cells] 1 = a two-ring tile must begin at this position of the order; empty: none
@@ -346,6 +344,8 @@ inline bool conn_pays(const Handle *h, int n_cells_of_launch, bool arithmetic_bo
     const int o = h->opt[SWE2D_OPT_COMPACT_IDX];
     return h->idxc && o != 0 && (o == 2 || (n_cells_of_launch >= 250000 && !arithmetic_bound));
 }
+inline TileSet &pair_tiles(Handle *h) { return h->npc == 4 ? h->fuseq : h->fuse; }     // the stage pair's tables for the handle's cell type
+void free_tiles(TileSet &ts);
 int fuse12_build(Handle *h);
 int launch_fuse12(Handle *h, int cell_end);
 int fuse123_build(Handle *h);

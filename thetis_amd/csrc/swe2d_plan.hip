@@ -69,7 +69,6 @@ bool fuse12_tiles_pay(const Handle *h, int n_tiles)
 {
     return forced_pair(h) || (double)h->n_cells/n_tiles >= (h->n_owned == h->n_cells ? kPairMinInteriorWhole : kPairMinInteriorPartition);
 }
-static bool fuse12_ready(const Handle *h) { return h->npc == 4 ? h->fuseq_tile != nullptr : h->fuse_tile != nullptr; }
 bool flow_fits(Handle *h) { return ((h->flow_blocks + 7)/8)*8 <= flow_capacity(h); }        // every block of a flow launch resident at once
 
 StepPath step_plan(Handle *h, StepCaller who, StepPath at_most)
@@ -98,11 +97,11 @@ int step_ready(Handle *h, StepCaller who, StepPath at_most, StepPath *path)
     StepPath p = step_plan(h, who, at_most);
     if (p == kTriple) {
         if (int rc = fuse123_build(h)) return rc;
-        if (!h->fuse3_tile) p = step_plan(h, who, kPair);
+        if (!h->fuse3.tile) p = step_plan(h, who, kPair);
     }
     if (p == kPair) {
         if (int rc = fuse12_build(h)) return rc;
-        if (!fuse12_ready(h)) p = kStages;
+        if (!pair_tiles(h).tile) p = kStages;
     }
     *path = p;
     return SWE2D_OK;

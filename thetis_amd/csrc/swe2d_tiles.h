@@ -1,0 +1,136 @@
+// swe2d_tiles.h - the tile tables of the fused stage kernels (swe2d_fuse.h): which cells a workgroup holds, on which lane, and where
+// each facet finds its neighbour.  Host integer logic only: no HIP header, no handle (tests/tile_tables_main.cpp runs it by itself).
+//
+// A tile = consecutive cells of an order (the interior) + ring 1, every cell that shares a facet with an interior cell + (two-ring
+// tiles) ring 2, the facet neighbours of ring 1.  The interior grows cell by cell while the caps of the TileSpec hold - and, where the
+// caller marks positions of the order as tile starts, up to the next mark.  ROLES are numbered [interior in the order added | ring 1 |
+// ring 2], each ring in the order of discovery without the cells that moved inwards later; the rest of the wg lanes is padding.
+// Per role and facet the table holds a 10-bit field: the lane of the neighbour in the tile (a boundary facet: the lane itself) or,
+// with bit 9 set, the staging slot of a neighbour outside the tile - only facets of the outermost ring lead there, slots are counted
+// per tile in role order.  How the fields are packed into device records is the caller's (swe2d_api_fuse.hip).
+//
+// Lanes: role r sits on the physical lane (r + 64*rot) & (wg - 1); rot = 0 unless the spec rotates.  In the three-stage kernel the wave
+// that holds the last 64 roles runs two stage bodies, the other three run three; which wave that is follows from rot, and rot from the
+// tile number by SWE_FUSE3_ROT - a host-side policy, the kernel reads it from its counts.  Not tile & 3: the XCD-chunked block map and
+// the dealing of workgroups over the compute units of an XCD can hand one compute unit tiles of a single residue.  The top two bits of
+// tile x 2^32/phi instead: every arithmetic progression of tile numbers meets the four values equally often.
+#pragma once
+#include <cstddef>
+#include <string>
+#include <utility>
+#include <vector>
+
+#ifndef SWE_FUSE3_ROT
+#define SWE_FUSE3_ROT(tile) ((int)(((unsigned)(tile)*0x9E3779B1u) >> 30))
+#endif
+
+namespace swe2d_impl {
+
+constexpr unsigned kTileOutside = 0x200u;             // facet field: bits [8:0] are a staging slot, not a lane
+
+struct TileSpec {
+    int nfacets;              // 3 | 4 facets per cell
+    int rings;                // 1 | 2
+    int wg;                   // lanes of a tile: the cap of interior + rings
+    int max_inner;            // cap of the interior
+    int max_ring1;            // cap of ring 1; < 0: only the total is bounded
+    int max_out;              // staging slots: (nfacets - 1) per cell of the outermost ring must fit
+    bool rotate;              // rot of tile t = SWE_FUSE3_ROT(t), else 0
+};
+
+struct TileTable {
+    std::vector<int> cell;                 // [n_tiles*wg] cell or -1, by physical lane
+    std::vector<unsigned> facet;           // [n_tiles*wg*nfacets] 10-bit fields, by physical lane
+    std::vector<int> n_inner, n_mid, rot;  // [n_tiles]: roles below n_inner are interior, below n_mid ring 1
+    long long ring[2] = {0, 0};            // cells of ring 1 / ring 2 over all tiles
+};
+
+// nbr: packed neighbour codes [nfacets][stride], (neighbour << 2) | its facet, or -marker on the boundary.  order: a permutation of
+// the cells, or null for the numbering.  start: [n_cells] 1 = a tile begins at this position of the order, or null.
+// Returns 0, or 1 with the reason in err (the mesh does not fit the caps, or the bookkeeping found itself wrong).
+inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *order, const unsigned char *start,
+                       const TileSpec &sp, TileTable &t, std::string &err)
+{
+    const int n = n_cells, nf = sp.nfacets, wg = sp.wg;
+    const char *who = sp.rings == 2 ? "fused stages: " : "fused stage pair: ";
+    t = TileTable();
+    std::vector<unsigned char> state((size_t)n, 0);                // 0 outside | 1 interior | 2 ring 1 | 3 ring 2, of the tile being built
+    std::vector<int> lane_of((size_t)n, -1), touched, inner;
+    std::vector<std::pair<int, unsigned char>> undo;
+    int count[4] = {0, 0, 0, 0};
+    auto set = [&](int c, unsigned char ns) {
+        undo.push_back({c, state[c]});
+        if (state[c] == 0) touched.push_back(c);
+        count[state[c]]--; state[c] = ns; count[ns]++;
+    };
+    for (int pos = 0; pos < n;) {
+        inner.clear(); touched.clear();
+        count[1] = count[2] = count[3] = 0;
+        while (pos < n && (int)inner.size() < sp.max_inner) {
+            if (start && start[pos] && !inner.empty()) break;      // the caller's tiles: compact patches
+            const int kk = order ? order[pos] : pos;
+            undo.clear();
+            const size_t touched_before = touched.size();
+            set(kk, 1);
+            for (int f = 0; f < nf; f++) {
+                const int code = nbr[(size_t)f*stride + kk];
+                if (code < 0) continue;
+                const int c1 = code >> 2;
+                if (state[c1] == 0 || state[c1] == 3) {
+                    set(c1, 2);
+                    for (int g = 0; sp.rings == 2 && g < nf; g++) {
+                        const int code2 = nbr[(size_t)g*stride + c1];
+                        if (code2 >= 0 && state[code2 >> 2] == 0) set(code2 >> 2, 3);
+                    }
+                }
+            }
+            if (count[1] + count[2] + count[3] > wg || (sp.max_ring1 >= 0 && count[2] > sp.max_ring1) || (nf - 1)*count[sp.rings + 1] > sp.max_out) {
+                if (inner.empty()) {
+                    err = std::string(who) + (sp.rings == 2 ? "a cell whose two rings do not fit a tile" : "a cell with more neighbours than a ring holds");
+                    return 1;
+                }
+                for (size_t i = undo.size(); i-- > 0;) { count[state[undo[i].first]]--; state[undo[i].first] = undo[i].second; count[undo[i].second]++; }
+                touched.resize(touched_before);
+                break;
+            }
+            inner.push_back(kk);
+            pos++;
+        }
+        // roles: the interior in the order it was added, ring 1, ring 2 (in the order of discovery)
+        std::vector<int> cells(inner);
+        for (int want = 2; want <= 3; want++)
+            for (int c : touched) if (state[c] == want) cells.push_back(c);
+        const int ni = (int)inner.size(), nm = ni + count[2], nt = (int)cells.size();
+        if (nt != count[1] + count[2] + count[3] || ni != count[1] || nt > wg) { err = std::string(who) + "tile bookkeeping"; return 1; }
+        const int tile = (int)t.n_inner.size();
+        const int rot = sp.rotate ? SWE_FUSE3_ROT(tile) & 3 : 0;
+        auto phys = [rot, wg](int role) { return (role + 64*rot) & (wg - 1); };
+        for (int l = 0; l < nt; l++) lane_of[cells[l]] = phys(l);
+        const size_t base = (size_t)tile*wg;
+        t.cell.resize(base + wg, -1);
+        t.facet.resize((base + wg)*nf, 0u);
+        const int outermost = sp.rings == 2 ? nm : ni;             // the first role that may have a neighbour outside the tile
+        int n_out = 0;
+        for (int l = 0; l < nt; l++) {
+            const int c = cells[l];
+            t.cell[base + phys(l)] = c;
+            for (int f = 0; f < nf; f++) {
+                const int code = nbr[(size_t)f*stride + c];
+                unsigned field;
+                if (code < 0) field = (unsigned)phys(l);                             // boundary facet: the cell itself
+                else if (state[code >> 2] != 0) field = (unsigned)lane_of[code >> 2];
+                else {
+                    if (l < outermost || n_out >= sp.max_out) { err = std::string(who) + "ring bookkeeping"; return 1; }
+                    field = kTileOutside | (unsigned)n_out++;
+                }
+                t.facet[(base + phys(l))*nf + f] = field;
+            }
+        }
+        t.n_inner.push_back(ni); t.n_mid.push_back(nm); t.rot.push_back(rot);
+        t.ring[0] += count[2]; t.ring[1] += count[3];
+        for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
+    }
+    return 0;
+}
+
+}  // namespace swe2d_impl
