@@ -568,6 +568,30 @@ int  swe2d_turbine_rows_reserve(swe2d_handle *h, int32_t capacity);
 int  swe2d_turbine_rows_append(swe2d_handle *h);
 int  swe2d_turbine_rows_read(swe2d_handle *h, double *out, int32_t *n_rows);
 
+/* ---- Harmonic tidal elevation on open boundaries (thetis/forcing.py, TidalBoundaryForcing.set_tidal_field):
+ *     eta_b(x, t) = mean(x) + sum_k amp_k(x) cos(omega_k t - phase_k(x))
+ * evaluated on the device for the end nodes of the listed boundary facets, into the planes swe2d_set_bc_facets(h, 0, ...) writes
+ * (markers take them with SWE2D_BC_ELEV_FIELD).  The argument and the running sum are formed left to right without contraction.
+ * A handle with a tide table steps by stage launches with one tide launch in front of each, all enqueued by the one swe2d_advance /
+ * swe2d_advance_forward_euler / swe2d_advance_coupled call; the fused kernels and the dataflow kernel decline it as they decline
+ * turbine farms (the *_info calls and swe2d_flow_supported report 0; swe2d_solve_flow, swe2d_solve_step_cells and
+ * swe2d_solve_stage_pair_cells return SWE2D_ERR_UNSUPPORTED).  The time is a kernel argument: inside a stream capture those advances
+ * and every swe2d_tide_* call return SWE2D_ERR_UNSUPPORTED.  No reference counterpart at the C level. */
+#define SWE2D_MAX_TIDE_CONSTITUENTS 32
+/* Sets (or replaces) the table: n_facets (cell, facet) pairs in the caller's cell numbering as in swe2d_set_bc_facets, n_constituents
+ * in 1 .. SWE2D_MAX_TIDE_CONSTITUENTS, omega[n_constituents], mean[n_facets][2], amp and phase [n_constituents][n_facets][2] (the two
+ * end nodes of a facet: the cell's nodes facet and facet + 1).  Allocates the elevation planes if absent.  Keeps the clock. */
+int  swe2d_tide_set(swe2d_handle *h, int32_t n_facets, const int32_t *cells, const int32_t *facets, int32_t n_constituents,
+                    const double *omega, const double *mean, const double *amp, const double *phase);
+int  swe2d_tide_clear(swe2d_handle *h);
+/* The clock of the advances: step k of the next one starts at t_k = t_base + (double)(k_first + k)*dt - never an accumulated sum -,
+ * its stage i is evaluated at t_k + c_i*dt, c = (0, 1, 1/2) (ForwardEuler: t_k + dt).  An advance of n steps adds n to k_first. */
+int  swe2d_tide_clock(swe2d_handle *h, double t_base, int64_t k_first);
+/* One launch at an explicit time (asynchronous): what the step-by-step path calls before swe2d_solve_stage. */
+int  swe2d_tide_eval(swe2d_handle *h, double t);
+/* The values the elevation planes hold for the listed facets, out[n_facets][2].  Synchronous. */
+int  swe2d_tide_read(swe2d_handle *h, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ ABI_VERSION = 12         # include/swe2d.h SWE2D_ABI_VERSION
 OPT_COUNT = 15
 SNAPSHOT_SLOTS = 2
 MAX_FARMS, MAX_THRUST_TABLE = 8, 16   # include/swe2d.h SWE2D_MAX_FARMS, SWE2D_MAX_THRUST_TABLE
+MAX_TIDE_CONSTITUENTS = 32            # include/swe2d.h SWE2D_MAX_TIDE_CONSTITUENTS
 PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
@@ -207,6 +208,11 @@ SYMBOLS = {
     'swe2d_turbine_rows_reserve': (ctypes.c_int, [_H, ctypes.c_int32]),
     'swe2d_turbine_rows_append': (ctypes.c_int, [_H]),
     'swe2d_turbine_rows_read': (ctypes.c_int, [_H, _dp, _ip]),
+    'swe2d_tide_set': (ctypes.c_int, [_H, ctypes.c_int32, _ip, _ip, ctypes.c_int32, _dp, _dp, _dp, _dp]),
+    'swe2d_tide_clear': (ctypes.c_int, [_H]),
+    'swe2d_tide_clock': (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int64]),
+    'swe2d_tide_eval': (ctypes.c_int, [_H, ctypes.c_double]),
+    'swe2d_tide_read': (ctypes.c_int, [_H, _dp]),
 }
 
 _lib = None

@@ -209,10 +209,11 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         """coupled_timeintegrator_2d.py:93-113"""
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
         fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
-        if update_forcings is None and fused:        # all SSPRK33: one C call per time step
+        if update_forcings is None and fused and not self.swe.forced_per_stage:        # all SSPRK33: one C call per time step
             self.swe._sync_to_device()
             for ts in self.tracers.values():
                 ts._sync_to_device()
+            self.swe._tide_clock(t)
             self.device.advance_coupled(1, tracer_only=self.options.tracer_only, use_limiter=use_limiter)
             self.swe._device_ahead = True
             for ts in self.tracers.values():
@@ -227,20 +228,30 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             if use_limiter:
                 self.device.tracer_limit(ts.tid)
 
-    def advance_steps(self, t, n_steps, probes=None):
+    @property
+    def forced_per_stage(self):
+        return self.swe.forced_per_stage
+
+    @property
+    def wants_clock(self):
+        return self.swe.wants_clock
+
+    def advance_steps(self, t, n_steps, probes=None, clock=None):
         """``n_steps`` coupled steps without forcing updates; one library call when every stepper is SSPRK33.  ``probes``: probe
-        sets of the device that take one row after every step (FlowSolver2d.create_iterator)."""
+        sets of the device that take one row after every step (FlowSolver2d.create_iterator).  ``clock`` = (t_start, n_done) of
+        the time loop, for a tide the device evaluates (SSPRK33.advance_steps)."""
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
         fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
         if not fused:
             for i in range(int(n_steps)):
-                self.advance(t + i*self.swe.dt)
+                self.advance(t + i*self.swe.dt if clock is None else clock[0] + (clock[1] + i)*self.swe.dt)
                 for pid in probes or ():
                     self.device.probe_append(pid)
             return
         self.swe._sync_to_device()
         for ts in self.tracers.values():
             ts._sync_to_device()
+        self.swe._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
             for _ in range(int(n_steps)):
                 self.device.advance_coupled(1, tracer_only=self.options.tracer_only, use_limiter=use_limiter)

@@ -258,6 +258,17 @@ struct Handle {
     int farm_blocks = 0;                                // blocks of a power launch
     unsigned long long *farm_rows = nullptr;            // [farm_rows_cap + 1][SWE_FARM_ROW] limb sums; the last row is swe2d_turbine_power's
     int farm_rows_cap = 0, farm_rows_n = 0;
+    // harmonic tidal boundary elevation (swe2d_tide.hip): n > 0 = the handle has a tide table
+    struct Tide {
+        int n = 0, K = 0;                               // boundary facets, constituents
+        double omega[SWE2D_MAX_TIDE_CONSTITUENTS] = {0.0};
+        double *tab = nullptr;                          // mean [2n] | amp [K][2n] | phase [K][2n]
+        int *list = nullptr;                            // device cells [n] | facets [n]
+        double *out = nullptr;                          // [2n] staging of swe2d_tide_read
+        double t_base = 0.0;                            // swe2d_tide_clock: step k of the next advance starts at t_base + (k_first + k)*dt
+        long long k_first = 0;
+    };
+    Tide tide;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -388,6 +399,11 @@ size_t p2p_channel_offset(const int *width, int c, int n_recv);
 void probe_free_all(Handle *h);
 // ---- tidal turbine farms (swe2d_turbine.hip): frees every farm and the power rows (swe2d_destroy)
 void farm_free_all(Handle *h);
+// ---- harmonic tidal boundary elevation (swe2d_tide.hip)
+void tide_free(Handle *h);                              // frees the table (swe2d_destroy)
+int tide_launch(Handle *h, double t);                   // one launch: the boundary elevation at time t into the elevation planes of bc_field
+double tide_stage_time(const Handle *h, int step, int i_stage);   // time of a stage of step `step` of the advance being enqueued (i_stage < 0: ForwardEuler)
+int tide_refuse_capture(Handle *h);                     // SWE2D_ERR_UNSUPPORTED where a handle with a tide is stepped inside a stream capture
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

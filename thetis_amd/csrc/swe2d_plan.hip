@@ -17,6 +17,7 @@ unsigned step_kernels(const Handle *h)
     if (h->wd) k &= (h->par.use_nonlinear_equations && opt_on(h, SWE2D_OPT_FLOW_WD)) ? kFlow : 0u;
     if (h->visc) k = 0;                                      // viscosity: a pass after each stage launch (swe2d_sipg.h)
     if (h->n_farms > 0) k = 0;                               // tidal turbine farms: the stage kernels carry the term (swe_source_terms<true>)
+    if (h->tide.n > 0) k = 0;                                // tidal boundary table: one tide launch in front of every stage launch (step_swe)
     if (h->opt[SWE2D_OPT_BND_INLINE] == 0) k = 0;            // the epilogue variant was asked for: stage kernels only
     if (h->h_nbr.empty()) k &= ~(kPair | kTriple);           // the tiles are cut from the host copy of the neighbour codes
     if (!h->flow_flag || !h->flow_ex) k &= ~kFlow;           // the dataflow kernel's tables (flow_build)
@@ -121,10 +122,29 @@ int step_launch(Handle *h, StepPath path, int i)
     return stage_on_range(h, i, 0, h->n_owned);
 }
 
+int tide_refuse_capture(Handle *h)
+{
+    // the time is a kernel argument: a replay of the captured launches would repeat it
+    if (h->tide.n > 0 && stream_capturing(h))
+        return fail(h, SWE2D_ERR_UNSUPPORTED, "a handle with a tide table cannot be stepped inside a stream capture (the time is a kernel argument)");
+    return SWE2D_OK;
+}
+
 int step_swe(Handle *h, StepCaller who, int n_steps)
 {
     StepPath path;
     if (n_steps <= 0) return SWE2D_OK;
+    if (h->tide.n > 0) {
+        // stage launches, the boundary elevation of the stage's time in front of each; the clock moves on by the steps made
+        if (int rc = tide_refuse_capture(h)) return rc;
+        for (int k = 0; k < n_steps; k++)
+            for (int i = 0; i < 3; i++) {
+                if (int rc = tide_launch(h, tide_stage_time(h, k, i))) return rc;
+                if (int rc = stage_on_range(h, i, 0, h->n_owned)) return rc;
+            }
+        h->tide.k_first += n_steps;
+        return SWE2D_OK;
+    }
     if (int rc = whole_step_path(h, who, &path)) return rc;
     if (path == kFlow) {
         int32_t ends[SWE_FLOW_MAX_STAGES];

@@ -15,3 +15,4 @@
 #include "swe2d_k_tracer.hip"
 #include "swe2d_probe.hip"
 #include "swe2d_turbine.hip"
+#include "swe2d_tide.hip"

@@ -31,6 +31,11 @@ class FacetValues(object):
         self.values = np.asarray(values, dtype=np.float64)
 
 
+class TideValues(object):
+    """Boundary elevation of one marker that the device evaluates itself from its tide table (``Swe2dDevice.tide_set``, which
+    must have listed the marker's facets): ``set_bc`` marks the marker Function-valued and uploads nothing."""
+
+
 class Swe2dDevice(object):
     def __init__(self, mesh, bathymetry_vertex, dt, g_grav=9.81, use_nonlinear_equations=True,
                  use_lax_friedrichs_velocity=True, lax_friedrichs_velocity_scaling_factor=1.0,
@@ -232,7 +237,9 @@ class Swe2dDevice(object):
         for key, value in (funcs or {}).items():
             if key == 'elev':
                 kind |= _lib.BC_ELEV
-                if is_field(value):
+                if isinstance(value, TideValues):
+                    kind |= _lib.BC_ELEV_FIELD
+                elif is_field(value):
                     kind |= _lib.BC_ELEV_FIELD
                     self._set_bc_function(0, marker, value)
                 else:
@@ -653,6 +660,43 @@ class Swe2dDevice(object):
         n = ctypes.c_int32()
         self._ck(self.lib.swe2d_turbine_rows_read(self.h, _ptr(out), ctypes.byref(n)))
         return out[:n.value].copy()
+
+    # -- harmonic tidal boundary elevation: csrc/swe2d_tide.hip
+    def tide_set(self, slots, omegas, mean, amp, phase):
+        """The tide table of the boundary facets of the marker slots ``slots``, in the order of ``boundary_facets`` slot after slot:
+        ``omegas`` (K,), ``mean`` (n, 2), ``amp`` / ``phase`` (K, n, 2) at the facets' end nodes."""
+        lists = [self.boundary_facets(sl) for sl in slots]
+        cells = np.ascontiguousarray(np.concatenate([self._device_cells(c) for c, _ in lists]), dtype=np.int32)
+        facets = np.ascontiguousarray(np.concatenate([f for _, f in lists]), dtype=np.int32)
+        n = len(cells)
+        om = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        K = len(om)
+        if not 1 <= K <= _lib.MAX_TIDE_CONSTITUENTS:
+            raise NotImplementedError('{:d} tidal constituents: 1 .. SWE2D_MAX_TIDE_CONSTITUENTS = {:d} are supported'.format(
+                K, _lib.MAX_TIDE_CONSTITUENTS))
+        m = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(n, 2))
+        a = np.ascontiguousarray(np.asarray(amp, dtype=np.float64).reshape(K, n, 2))
+        p = np.ascontiguousarray(np.asarray(phase, dtype=np.float64).reshape(K, n, 2))
+        self._ck(self.lib.swe2d_tide_set(self.h, n, _iptr(cells), _iptr(facets), K, _ptr(om), _ptr(m), _ptr(a), _ptr(p)))
+        self._tide_n = n
+
+    def tide_clear(self):
+        self._ck(self.lib.swe2d_tide_clear(self.h))
+        self._tide_n = 0
+
+    def tide_clock(self, t_base, k_first=0):
+        """step k of the next advance starts at ``t_base + (k_first + k)*dt``; an advance of n steps adds n to ``k_first``"""
+        self._ck(self.lib.swe2d_tide_clock(self.h, float(t_base), int(k_first)))
+
+    def tide_eval(self, t):
+        """one launch: the boundary elevation of time ``t`` (enqueued; what the step-by-step path calls before ``solve_stage``)"""
+        self._ck(self.lib.swe2d_tide_eval(self.h, float(t)))
+
+    def tide_read(self):
+        """the values the device holds at the table's facet nodes, (n, 2) in the order of ``tide_set``"""
+        out = np.empty((max(getattr(self, '_tide_n', 0), 1), 2))
+        self._ck(self.lib.swe2d_tide_read(self.h, _ptr(out)))
+        return out[:getattr(self, '_tide_n', 0)]
 
     # -- tracers + limiter
     def _nodal_in(self, a):

@@ -13,6 +13,8 @@ import numpy as np
 
 from . import _lib
 from .spmd import make_device
+from .device import TideValues
+from .forcing import HarmonicTidalForcing
 from .function import Function
 from .options import Constant
 from .shallowwater_eq import g_grav
@@ -127,6 +129,11 @@ class ERKGenericShuOsher(TimeIntegrator):
         self._uploaded_version = None
         self._device_ahead = False
         self._farm_signatures = {}               # farm index -> signature of the density uploaded last (_push_farms)
+        # HarmonicTidalForcing objects given as a boundary's 'elev' (_push_bcs): the one whose table the device evaluates itself in
+        # front of every stage, or - a device class without tide tables, several ranks - those the host evaluates per stage
+        self._device_tide = None
+        self._device_tide_signature = None
+        self._host_tides = []
         if equation.depth.use_wetting_and_drying:
             alpha = equation.depth.wetting_and_drying_alpha
             if isinstance(alpha, Function):
@@ -266,9 +273,15 @@ class ERKGenericShuOsher(TimeIntegrator):
         did not change since the last upload are skipped (a Function-valued boundary costs a nodal field copy)."""
         mesh = self.equation.mesh
         cache = self.__dict__.setdefault('_bc_signatures', {})
+        on_device = self._push_tide()
+
+        def signature(v):
+            if isinstance(v, HarmonicTidalForcing):
+                return ('t', id(v)) if on_device else ('t', id(v)) + self._signature(v.elev_field)
+            return self._signature(v)
         for marker in mesh.boundary_markers:
             funcs = self.bnd_conditions.get(marker)
-            sig = None if funcs is None else tuple(sorted((k, self._signature(v)) for k, v in funcs.items()))
+            sig = None if funcs is None else tuple(sorted((k, signature(v)) for k, v in funcs.items()))
             if marker in cache and cache[marker] == sig:
                 continue
             cache[marker] = sig
@@ -279,6 +292,11 @@ class ERKGenericShuOsher(TimeIntegrator):
             for key, v in funcs.items():
                 if key not in ('elev', 'uv', 'un', 'flux', 'drag'):
                     raise Exception('Invalid boundary tag "{:}" specified on boundary {:}'.format(key, marker))
+                if isinstance(v, HarmonicTidalForcing):
+                    if on_device:                # the device writes these facets' values itself (tide_set listed them)
+                        vals[key] = TideValues()
+                        continue
+                    v = v.elev_field             # the host evaluates it per stage (_stage_forcings): a Function-valued boundary
                 if isinstance(v, Function):
                     # Function-valued boundary data (e.g. a tidal elevation field): nodal values at the DG nodes
                     if key not in ('elev', 'uv', 'un', 'flux'):
@@ -297,6 +315,75 @@ class ERKGenericShuOsher(TimeIntegrator):
                 else:
                     vals[key] = _const_value(v)
             self.device.set_bc(marker, vals)
+
+    def _push_tide(self):
+        """Find the HarmonicTidalForcing objects among the boundary values and hand the table to the device (once: the tables of a
+        forcing object do not change).  Returns whether the device evaluates the tide itself; otherwise ``_host_tides`` lists the
+        objects whose ``set_tidal_field`` runs on the host in front of every stage - the same values through the compact upload."""
+        mesh = self.equation.mesh
+        found = []                               # (marker, forcing)
+        for marker in mesh.boundary_markers:
+            for key, v in (self.bnd_conditions.get(marker) or {}).items():
+                if isinstance(v, HarmonicTidalForcing):
+                    if key != 'elev':
+                        raise NotImplementedError("a HarmonicTidalForcing under '{:}' (boundary {:}): only 'elev' tides are "
+                                                  "implemented".format(key, marker))
+                    if v.elev_field.function_space().mesh() is not mesh:
+                        raise ValueError('the HarmonicTidalForcing of boundary {:} lives on another mesh'.format(marker))
+                    if v.boundary_ids is not None and int(marker) not in v.boundary_ids:
+                        raise ValueError('boundary {:} is not among the boundary_ids {:} of its HarmonicTidalForcing'.format(
+                            marker, v.boundary_ids))
+                    found.append((marker, v))
+        several_ranks = self.comm is not None and self.comm.size > 1
+        on_device = bool(found) and hasattr(self.device, 'tide_set') and not several_ranks
+        objs = []
+        for _, v in found:
+            if not any(v is o for o in objs):
+                objs.append(v)
+        if on_device and len(objs) > 1:
+            raise NotImplementedError('several HarmonicTidalForcing objects on one solver: the device holds one tide table (one set of '
+                                      'constituents); give every tidal boundary the same object')
+        self._host_tides = [] if on_device else objs
+        if on_device:
+            f = objs[0]
+            markers = [m for m, _ in found]
+            sig = (id(f), tuple(markers))
+            if sig != self._device_tide_signature:
+                tabs = [f.facet_tables(self.device, m) for m in markers]
+                self.device.tide_set([self.device._slot(m) for m in markers], f.omegas, np.concatenate([t[0] for t in tabs]),
+                                     np.concatenate([t[1] for t in tabs], axis=1), np.concatenate([t[2] for t in tabs], axis=1))
+                self._device_tide_signature = sig
+            self._device_tide = f
+        elif self._device_tide is not None:
+            self.device.tide_clear()
+            self._device_tide, self._device_tide_signature = None, None
+        return on_device
+
+    @property
+    def forced_per_stage(self):
+        """a forcing the HOST evaluates in front of every stage even without ``update_forcings``: no batched steps"""
+        return bool(self._host_tides)
+
+    @property
+    def wants_clock(self):
+        """the device evaluates a tide: ``advance_steps`` takes the time loop's ``clock=(t_start, n_done)``"""
+        return self._device_tide is not None
+
+    def _tide_clock(self, t_base, k_first=0):
+        if self._device_tide is not None:
+            self.device.tide_clock(t_base, k_first)
+
+    def _stage_forcings(self, t_stage, update_forcings, eval_tide=True):
+        """what precedes a stage evaluated at ``t_stage``: the tide, then the user's ``update_forcings``, then the uploads"""
+        if eval_tide and self._device_tide is not None:
+            self.device.tide_eval(t_stage)
+        for f in self._host_tides:
+            f.set_tidal_field(t_stage)
+        if update_forcings is not None:
+            update_forcings(t_stage)
+        if update_forcings is not None or self._host_tides:
+            self._push_bcs()
+            self._push_fields(only_changed=True)
 
     # ---- host <-> device state
     def _host_version(self):
@@ -336,10 +423,7 @@ class ERKGenericShuOsher(TimeIntegrator):
 
     def solve_stage(self, i_stage, t, update_forcings=None):
         """Solve i-th stage and assign solution to :attr:`self.solution` (rungekutta.py:930-946)."""
-        if update_forcings is not None:
-            update_forcings(t + self.c[i_stage]*self.dt)
-            self._push_bcs()
-            self._push_fields(only_changed=True)
+        self._stage_forcings(t + self.c[i_stage]*self.dt, update_forcings)
         if i_stage == 0:
             self._sync_to_device()
         # (host WRITES to `solution` between the stages of a step are not supported: the device keeps U0 and the stage solutions
@@ -350,8 +434,9 @@ class ERKGenericShuOsher(TimeIntegrator):
 
     def advance(self, t, update_forcings=None):
         """Advances equations for one time step (rungekutta.py:949-952)."""
-        if update_forcings is None:
+        if update_forcings is None and not self._host_tides:
             self._sync_to_device()
+            self._tide_clock(t)
             self.device.advance(1)
             self._last_stage = 2
             self._device_ahead = True
@@ -359,11 +444,14 @@ class ERKGenericShuOsher(TimeIntegrator):
             for i in range(self.n_stages):
                 self.solve_stage(i, t, update_forcings)
 
-    def advance_steps(self, t, n_steps, probes=None):
+    def advance_steps(self, t, n_steps, probes=None, clock=None):
         """``n_steps`` time steps without forcing updates in ONE call into the library (FlowSolver2d.iterate batches the
         steps between exports: no Python between the launches).  ``probes``: ids of probe sets of the device that take one row
-        after every step - then a step launch and the row launches alternate (enqueued, no synchronisation)."""
+        after every step - then a step launch and the row launches alternate (enqueued, no synchronisation).
+        ``clock`` = (t_start, n_done) of the time loop: a tide on the device is evaluated at t_start + (n_done + k)*dt + c_i*dt, the
+        loop's own arithmetic (the library counts the steps on)."""
         self._sync_to_device()
+        self._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
             for _ in range(int(n_steps)):
                 self.device.advance(1)
@@ -396,16 +484,16 @@ class ForwardEuler(ERKGenericShuOsher):
         self.advance(t, update_forcings)
 
     def advance(self, t, update_forcings=None):
-        if update_forcings is not None:
-            update_forcings(t + self.dt)            # the reference evaluates the forcings at the NEW time (:161-162)
-            self._push_bcs()
-            self._push_fields(only_changed=True)
+        # the reference evaluates the forcings at the NEW time (:161-162); a tide on the device: the library's own launch, by the clock
+        self._stage_forcings(t + self.dt, update_forcings, eval_tide=False)
         self._sync_to_device()
+        self._tide_clock(t)
         self.device.advance_forward_euler(1)
         self._device_ahead = True
 
-    def advance_steps(self, t, n_steps, probes=None):
+    def advance_steps(self, t, n_steps, probes=None, clock=None):
         self._sync_to_device()
+        self._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
             for _ in range(int(n_steps)):
                 self.device.advance_forward_euler(1)

@@ -459,7 +459,11 @@ class FlowSolver2d(object):
         # step-by-step loop.  Anything else (a host callback, several ranks) takes the step-by-step loop.
         # (a TurbineFunctionalCallback appends power rows the same way)
         batch_rows = bool(step_cbs) and self.comm.size == 1 and all(hasattr(cb, 'row_probe') for cb in step_cbs)
+        # (a HarmonicTidalForcing as a boundary's 'elev' is evaluated by the device in front of every stage and keeps the batches:
+        #  the stepper gets the loop's clock; where the HOST has to evaluate it - forced_per_stage - the loop goes step by step)
+        clock = (lambda: {'clock': (t_start, n_done)}) if getattr(stepper, 'wants_clock', False) else (lambda: {})
         can_batch = (_batch and update_forcings is None and hasattr(stepper, 'advance_steps')
+                     and not getattr(stepper, 'forced_per_stage', False)
                      and (not step_cbs or (batch_rows and all(cb.row_probe(1) is not None for cb in step_cbs))))
 
         def steps_to_next_event():
@@ -481,9 +485,9 @@ class FlowSolver2d(object):
                         probes, n = None, 1
                         stepper.advance(self.simulation_time, update_forcings)
                     else:
-                        stepper.advance_steps(self.simulation_time, n, probes=[pid for _, pid in probes])
+                        stepper.advance_steps(self.simulation_time, n, probes=[pid for _, pid in probes], **clock())
                 else:
-                    stepper.advance_steps(self.simulation_time, n)
+                    stepper.advance_steps(self.simulation_time, n, **clock())
             else:
                 n = 1
                 stepper.advance(self.simulation_time, update_forcings)

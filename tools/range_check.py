@@ -26,7 +26,7 @@ def exercise():
         mesh, bath, uv, eta = case
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
-        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying'):
+        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'tide'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
             bath_v = bath - 0.6*bath.max() if variant == 'wetting-drying' else (bath + 20.0 if variant.startswith('farms') else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
@@ -68,6 +68,22 @@ def exercise():
                 dens[-1] = 0.0                       # ... whose farm-cell list ends one short of the last cell
                 dev.turbine_farm_set(3, par2, dens)
                 assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
+            if variant == 'tide':
+                # harmonic tidal boundary elevation: swe_tide_kernel reads its table and the facet list and writes the elevation planes
+                # of the boundary fields through the checked accesses, one launch in front of every stage launch of the advances below
+                # (the frequencies are kernel arguments)
+                from thetis_amd.device import TideValues
+                slot = dev._slot(markers[0])
+                nf, kc = len(dev.boundary_facets(slot)[0]), 5
+                rng = np.random.default_rng(7)
+                dev.tide_set([slot], 1.4e-4*(1.0 + np.arange(kc)), 0.1*rng.normal(size=(nf, 2)), 0.2*rng.uniform(size=(kc, nf, 2)),
+                             rng.uniform(0.0, 6.0, size=(kc, nf, 2)))
+                dev.set_bc(markers[0], {'elev': TideValues()})
+                dev.tide_clock(1000.0, 7)
+                dev.tide_eval(44714.1)
+                assert dev.tide_read().shape == (nf, 2) and np.isfinite(dev.tide_read()).all()
+                assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
+                n_launch += 12
             dev.set_state(0.1*uv, 0.1*np.abs(eta))
             if variant.startswith('farms'):
                 dev.turbine_rows_reserve(3)
