@@ -592,6 +592,28 @@ int  swe2d_tide_eval(swe2d_handle *h, double t);
 /* The values the elevation planes hold for the listed facets, out[n_facets][2].  Synchronous. */
 int  swe2d_tide_read(swe2d_handle *h, double *out);
 
+/* ---- Running field statistics: extrema, means and harmonic sums of the whole state over every sampled step.
+ * A statistics set holds 8 + 2K accumulators per DG node (K harmonic constituents, 0 <= K <= SWE2D_MAX_TIDE_CONSTITUENTS) in planes
+ * laid out like the state.  One sample takes e, u, v of every node as swe2d_get_state returns them (wetting-drying: eta, not the
+ * displaced depth) and updates, left to right without contraction,
+ *     q = u*u + v*v,  s = sqrt(q)
+ *     0: e_min = e < e_min ? e : e_min     1: e_max = e > e_max ? e : e_max     2: q_max = q > q_max ? q : q_max
+ *     3: e_sum += e    4: u_sum += u    5: v_sum += v    6: s_sum += s    7: s3_sum += q*s
+ *     8 + 2k: C_k += e*wc_k        9 + 2k: S_k += e*ws_k
+ * with the weights wc_k = cos(omega_k t), ws_k = sin(omega_k t) formed by the CALLER: the device evaluates no transcendental, and all
+ * accumulators but s_sum / s3_sum (the device's sqrt) have the bits of the same expressions evaluated on the host.  A new or reset
+ * set holds e_min = +inf, e_max = q_max = -inf and zeros.  Every statistics call inside a stream capture returns
+ * SWE2D_ERR_UNSUPPORTED.  No reference counterpart (the reference's AccumulatorCallback integrates a scalar in time, not fields). */
+int  swe2d_stats_create(swe2d_handle *h, int32_t n_constituents, int32_t *stats_id);
+/* one sample of the current state: ONE launch on the handle's stream, no synchronisation.  weights [2K]: wc_0, ws_0, wc_1, ...;
+ * may be NULL when K = 0 */
+int  swe2d_stats_append(swe2d_handle *h, int32_t stats_id, const double *weights);
+/* synchronises; out [8 + 2K][n_cells][nodes_per_cell] in the handle's cell numbering, n_samples = appends since create / reset.
+ * Does not clear. */
+int  swe2d_stats_read(swe2d_handle *h, int32_t stats_id, double *out, int64_t *n_samples);
+int  swe2d_stats_reset(swe2d_handle *h, int32_t stats_id);
+int  swe2d_stats_destroy(swe2d_handle *h, int32_t stats_id);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ OPT_COUNT = 15
 SNAPSHOT_SLOTS = 2
 MAX_FARMS, MAX_THRUST_TABLE = 8, 16   # include/swe2d.h SWE2D_MAX_FARMS, SWE2D_MAX_THRUST_TABLE
 MAX_TIDE_CONSTITUENTS = 32            # include/swe2d.h SWE2D_MAX_TIDE_CONSTITUENTS
+STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
 PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
@@ -213,6 +214,11 @@ SYMBOLS = {
     'swe2d_tide_clock': (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int64]),
     'swe2d_tide_eval': (ctypes.c_int, [_H, ctypes.c_double]),
     'swe2d_tide_read': (ctypes.c_int, [_H, _dp]),
+    'swe2d_stats_create': (ctypes.c_int, [_H, ctypes.c_int32, _ip]),
+    'swe2d_stats_append': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
+    'swe2d_stats_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_stats_reset': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_stats_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ import numpy as np
 from .function import Function
 from .log import print_output
 from .options import Constant
+from .rungekutta import advance_with_rows
 from .timeintegrator import TimeIntegratorBase
 
 __all__ = ['DeviceTracerSSPRK33', 'DeviceTracerForwardEuler', 'GeneralCoupledTimeIntegrator2D']
@@ -243,20 +244,23 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
         fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
         if not fused:
-            for i in range(int(n_steps)):
-                self.advance(t + i*self.swe.dt if clock is None else clock[0] + (clock[1] + i)*self.swe.dt)
-                for pid in probes or ():
-                    self.device.probe_append(pid)
+            done = [0]
+
+            def one_by_one(j):
+                for _ in range(j):
+                    i = done[0]
+                    self.advance(t + i*self.swe.dt if clock is None else clock[0] + (clock[1] + i)*self.swe.dt)
+                    done[0] += 1
+            advance_with_rows(self.device, n_steps, one_by_one, probes or (), self.swe._step_end_time(t, clock))
             return
         self.swe._sync_to_device()
         for ts in self.tracers.values():
             ts._sync_to_device()
         self.swe._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
-            for _ in range(int(n_steps)):
-                self.device.advance_coupled(1, tracer_only=self.options.tracer_only, use_limiter=use_limiter)
-                for pid in probes:
-                    self.device.probe_append(pid)
+            advance_with_rows(self.device, n_steps,
+                              lambda j: self.device.advance_coupled(j, tracer_only=self.options.tracer_only, use_limiter=use_limiter),
+                              probes, self.swe._step_end_time(t, clock))
         else:
             self.device.advance_coupled(int(n_steps), tracer_only=self.options.tracer_only, use_limiter=use_limiter)
         self.swe._device_ahead = True

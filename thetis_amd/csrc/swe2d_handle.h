@@ -269,6 +269,14 @@ struct Handle {
         long long k_first = 0;
     };
     Tide tide;
+    // running field statistics (swe2d_stats.hip): slot = statistics id; a destroyed set leaves an empty slot
+    struct Stats {
+        bool live = false;
+        int K = 0;                                      // harmonic constituents
+        double *acc = nullptr;                          // [8 + 2K][npc][stride] accumulator planes, laid out like the state
+        long long n_samples = 0;                        // appends since create / reset
+    };
+    std::vector<Stats> stats;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -404,6 +412,8 @@ void tide_free(Handle *h);                              // frees the table (swe2
 int tide_launch(Handle *h, double t);                   // one launch: the boundary elevation at time t into the elevation planes of bc_field
 double tide_stage_time(const Handle *h, int step, int i_stage);   // time of a stage of step `step` of the advance being enqueued (i_stage < 0: ForwardEuler)
 int tide_refuse_capture(Handle *h);                     // SWE2D_ERR_UNSUPPORTED where a handle with a tide is stepped inside a stream capture
+// ---- running field statistics (swe2d_stats.hip): frees every statistics set of the handle (swe2d_destroy)
+void stats_free_all(Handle *h);
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

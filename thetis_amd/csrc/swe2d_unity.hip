@@ -16,3 +16,4 @@
 #include "swe2d_probe.hip"
 #include "swe2d_turbine.hip"
 #include "swe2d_tide.hip"
+#include "swe2d_stats.hip"

@@ -698,6 +698,41 @@ class Swe2dDevice(object):
         self._ck(self.lib.swe2d_tide_read(self.h, _ptr(out)))
         return out[:getattr(self, '_tide_n', 0)]
 
+    # -- running field statistics: csrc/swe2d_stats.hip
+    def stats_create(self, n_constituents=0):
+        """A statistics set with ``n_constituents`` harmonic constituents (8 + 2K accumulators per DG node).  Returns its id."""
+        K = int(n_constituents)
+        sid = ctypes.c_int32()
+        self._ck(self.lib.swe2d_stats_create(self.h, K, ctypes.byref(sid)))
+        self.__dict__.setdefault('_stats_K', {})[sid.value] = K
+        return sid.value
+
+    def stats_append(self, sid, weights=None):
+        """one sample of the current state, enqueued (no synchronisation); ``weights`` (2K,): cos, sin of omega_k t, interleaved"""
+        K = self._stats_K[int(sid)]
+        w = None
+        if K:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.shape != (2*K,):
+                raise ValueError('statistics set {:d} takes {:d} weights'.format(int(sid), 2*K))
+        self._ck(self.lib.swe2d_stats_append(self.h, int(sid), None if w is None else _ptr(w)))
+
+    def stats_read(self, sid):
+        """(accumulators (8 + 2K, N, k) in the caller's cell numbering, samples since create / reset); synchronises, does not clear"""
+        K = self._stats_K[int(sid)]
+        out = np.empty((_lib.STATS_FIXED + 2*K, self.n_cells, self.npc))
+        n = ctypes.c_int64()
+        self._ck(self.lib.swe2d_stats_read(self.h, int(sid), _ptr(out), ctypes.byref(n)))
+        if self.perm is not None:
+            out = np.stack([self._nodal_out(a) for a in out])
+        return out, int(n.value)
+
+    def stats_reset(self, sid):
+        self._ck(self.lib.swe2d_stats_reset(self.h, int(sid)))
+
+    def stats_destroy(self, sid):
+        self._ck(self.lib.swe2d_stats_destroy(self.h, int(sid)))
+
     # -- tracers + limiter
     def _nodal_in(self, a):
         a = np.asarray(a, dtype=np.float64).reshape(self.n_cells, self.npc)

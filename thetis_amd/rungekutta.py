@@ -18,9 +18,32 @@ from .forcing import HarmonicTidalForcing
 from .function import Function
 from .options import Constant
 from .shallowwater_eq import g_grav
-from .timeintegrator import TimeIntegrator
+from .timeintegrator import StepConsumer, TimeIntegrator
 
-__all__ = ['ForwardEuler', 'SSPRK33Abstract', 'ERKGenericShuOsher', 'SSPRK33', 'butcher_to_shuosher_form']
+__all__ = ['ForwardEuler', 'SSPRK33Abstract', 'ERKGenericShuOsher', 'SSPRK33', 'butcher_to_shuosher_form', 'advance_with_rows']
+
+
+def advance_with_rows(device, n_steps, advance, probes, end_time):
+    """``n_steps`` steps of a batch whose ``probes`` take rows between the steps.  A probe is the id of a probe set of ``device``
+    (``Swe2dDevice.TURBINE_ROWS`` among them) - one row after EVERY step - or a ``timeintegrator.StepConsumer`` that is asked per step:
+    ``wants_append(k, t)`` with the step's index in the batch and the time it ends at, ``end_time(k)``, then ``append(device, k, t)``.
+    ``advance(j)`` issues j steps in one call into the library; steps after which nothing is appended are merged into one such call
+    (the state does not depend on how the steps are cut into calls)."""
+    pending = 0
+    for k in range(int(n_steps)):
+        pending += 1
+        t_k = end_time(k)
+        due = [p for p in probes if not isinstance(p, StepConsumer) or p.wants_append(k, t_k)]
+        if due:
+            advance(pending)
+            pending = 0
+            for p in due:
+                if isinstance(p, StepConsumer):
+                    p.append(device, k, t_k)
+                else:
+                    device.probe_append(p)
+    if pending:
+        advance(pending)
 
 
 def butcher_to_shuosher_form(a, b):
@@ -448,19 +471,22 @@ class ERKGenericShuOsher(TimeIntegrator):
         """``n_steps`` time steps without forcing updates in ONE call into the library (FlowSolver2d.iterate batches the
         steps between exports: no Python between the launches).  ``probes``: ids of probe sets of the device that take one row
         after every step - then a step launch and the row launches alternate (enqueued, no synchronisation).
+        A probe may also be an object that takes a row after SOME steps (``advance_with_rows``): the steps in between are one call.
         ``clock`` = (t_start, n_done) of the time loop: a tide on the device is evaluated at t_start + (n_done + k)*dt + c_i*dt, the
         loop's own arithmetic (the library counts the steps on)."""
         self._sync_to_device()
         self._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
-            for _ in range(int(n_steps)):
-                self.device.advance(1)
-                for pid in probes:
-                    self.device.probe_append(pid)
+            advance_with_rows(self.device, n_steps, self.device.advance, probes, self._step_end_time(t, clock))
         else:
             self.device.advance(int(n_steps))
         self._last_stage = 2
         self._device_ahead = True
+
+    def _step_end_time(self, t, clock):
+        """k -> the time step k of a batch ends at, by the time loop's own arithmetic t_start + n*dt (solver2d.py:1127)"""
+        t_start, n_done = clock if clock is not None else (t, 0)
+        return lambda k: t_start + (n_done + k + 1)*self.dt
 
     def diagnostics(self):
         """{int eta^2, int |u|^2, int (eta+h), min(h+eta)} of the device-resident state."""
@@ -495,10 +521,7 @@ class ForwardEuler(ERKGenericShuOsher):
         self._sync_to_device()
         self._tide_clock(*(clock if clock is not None else (t, 0)))
         if probes:
-            for _ in range(int(n_steps)):
-                self.device.advance_forward_euler(1)
-                for pid in probes:
-                    self.device.probe_append(pid)
+            advance_with_rows(self.device, n_steps, self.device.advance_forward_euler, probes, self._step_end_time(t, clock))
         else:
             self.device.advance_forward_euler(int(n_steps))
         self._device_ahead = True

@@ -25,6 +25,7 @@ from .function import Function, FunctionSpace, MixedFunction, get_functionspace
 from .log import print_output
 from .options import Constant, ModelOptions2d
 from .rungekutta import SSPRK33, ForwardEuler
+from .timeintegrator import StepConsumer
 from .shallowwater_eq import DepthExpression, ShallowWaterEquations, g_grav
 from .limiter import VertexBasedP1DGLimiter
 from .tracer_eq_2d import TracerEquation2D
@@ -457,7 +458,8 @@ class FlowSolver2d(object):
         # per-time-step callbacks keep the steps batched when every one of them is a device detector (callback.DetectorsCallback):
         # the device appends a row after every step, the rows are handed over after the batch - the times and values of the
         # step-by-step loop.  Anything else (a host callback, several ranks) takes the step-by-step loop.
-        # (a TurbineFunctionalCallback appends power rows the same way)
+        # (a TurbineFunctionalCallback appends power rows the same way; a FieldStatisticsCallback hands in ITSELF instead of a probe
+        #  id: the stepper asks it per step of the batch whether it samples, and merges the steps in between into one call)
         batch_rows = bool(step_cbs) and self.comm.size == 1 and all(hasattr(cb, 'row_probe') for cb in step_cbs)
         # (a HarmonicTidalForcing as a boundary's 'elev' is evaluated by the device in front of every stage and keeps the batches:
         #  the stepper gets the loop's clock; where the HOST has to evaluate it - forced_per_stage - the loop goes step by step)
@@ -485,7 +487,10 @@ class FlowSolver2d(object):
                         probes, n = None, 1
                         stepper.advance(self.simulation_time, update_forcings)
                     else:
-                        stepper.advance_steps(self.simulation_time, n, probes=[pid for _, pid in probes], **clock())
+                        # (a consumer that is asked per step gets the step's time: the loop's clock then goes along in any case)
+                        asked = any(isinstance(pid, StepConsumer) for _, pid in probes)
+                        stepper.advance_steps(self.simulation_time, n, probes=[pid for _, pid in probes],
+                                              **({'clock': (t_start, n_done)} if asked else clock()))
                 else:
                     stepper.advance_steps(self.simulation_time, n, **clock())
             else:
@@ -493,11 +498,12 @@ class FlowSolver2d(object):
                 stepper.advance(self.simulation_time, update_forcings)
             yield self.simulation_time                  # the time the step STARTED from, as the reference's generator does
             if probes is not None:
-                rows = [dev.probe_read(pid) for dev, pid in probes]
+                rows = [None if isinstance(pid, StepConsumer) else dev.probe_read(pid) for dev, pid in probes]
                 for k in range(n):                      # in the order the step-by-step loop evaluates them
                     t_k = t_start + (n_done + k + 1)*self.dt
                     for cb, r in zip(step_cbs, rows):
-                        cb.take_row(t_k, r[k])
+                        if r is not None:               # (None: the consumer took its samples itself, step by step of the batch)
+                            cb.take_row(t_k, r[k])
             n_done += n
             self.iteration += n
             self.simulation_time = t_start + n_done*self.dt          # k*dt, never an accumulated sum (solver2d.py:1127)

@@ -26,6 +26,21 @@ class TimeIntegratorBase(abc.ABC):
         """One time step starting at time ``t``; ``update_forcings(t_stage)`` is called before every stage evaluation."""
 
 
+class StepConsumer(abc.ABC):
+    """A consumer of a batch of steps (``advance_steps(..., probes=[...])``) that samples after SOME of them.  An integer probe id
+    takes a row after every step and is read after the batch; a StepConsumer is asked per step of the batch and appends itself, so
+    the driver hands it the loop's clock and reads no rows for it.  ``rungekutta.advance_with_rows`` and
+    ``FlowSolver2d.create_iterator`` tell the two kinds apart by this class alone."""
+
+    @abc.abstractmethod
+    def wants_append(self, k, t):
+        """Does step ``k`` of the batch, which ends at time ``t``, leave a sample?"""
+
+    @abc.abstractmethod
+    def append(self, device, k, t):
+        """Enqueue the sample after step ``k`` (time ``t``) on ``device``; the steps up to it have been issued."""
+
+
 class TimeIntegrator(TimeIntegratorBase):
     """A stepper bound to ONE equation: remembers what it marches, with which step, and under which name it logs."""
 

@@ -26,9 +26,10 @@ def exercise():
         mesh, bath, uv, eta = case
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
-        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'tide'):
+        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'tide', 'stats',
+                        'stats+wetting-drying'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
-            bath_v = bath - 0.6*bath.max() if variant == 'wetting-drying' else (bath + 20.0 if variant.startswith('farms') else bath)
+            bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
             markers = mesh.boundary_markers
             if variant == 'open+fields':
@@ -41,7 +42,7 @@ def exercise():
             if variant == 'viscosity':
                 dev.set_viscosity(20.0 + 5.0*np.arange(mesh.num_vertices)/mesh.num_vertices, use_grad_div_viscosity_term=True)
                 dev.set_bc(markers[0], {'un': 0.1})
-            if variant == 'wetting-drying':
+            if variant in ('wetting-drying', 'stats+wetting-drying'):
                 dev.set_wetting_and_drying(0.5)
                 dev.set_scalar(_lib.SCALAR_MANNING_DRAG, 0.02)
             if variant.startswith('farms'):
@@ -94,6 +95,22 @@ def exercise():
                 assert rows.shape[0] == 3 and np.isfinite(rows).all() and (rows[:, [0, 3]] >= 0).all() and rows[:, 3].min() > 0, rows
                 assert np.isfinite(dev.turbine_power()).all()
                 n_launch += 8
+            if variant.startswith('stats'):
+                # running field statistics: swe_stats_kernel reads the state planes (wetting-drying: also the cell vertices, alpha and the
+                # bathymetry) and read-modify-writes the accumulator planes of its set through the checked accesses; the weights are
+                # kernel arguments.  (swe_stats_fill_kernel writes through a plain pointer: host-checked size, the whole allocation.)
+                sets = {kc: dev.stats_create(kc) for kc in (0, 5, 32)}
+                for j in range(3):
+                    dev.advance(1)
+                    for kc, sid in sets.items():
+                        arg = 1.4e-4*(1.0 + np.arange(kc))*(44714.1 + 300.0*j)
+                        dev.stats_append(sid, np.stack([np.cos(arg), np.sin(arg)], axis=1).reshape(-1) if kc else None)
+                for kc, sid in sets.items():
+                    acc, n = dev.stats_read(sid)
+                    assert n == 3 and acc.shape == (8 + 2*kc, mesh.num_cells, k) and np.isfinite(acc).all(), (name, variant, kc)
+                    assert (acc[0] <= acc[1]).all() and (acc[2] >= 0).all()
+                dev.stats_destroy(sets[5])
+                n_launch += 12
             if variant == 'tracers':
                 tid = dev.add_tracer()
                 dev.tracer_set_state(tid, 1.0 + 0.1*np.random.default_rng(0).normal(size=(mesh.num_cells, k)))
