@@ -568,6 +568,31 @@ int  swe2d_turbine_rows_reserve(swe2d_handle *h, int32_t capacity);
 int  swe2d_turbine_rows_append(swe2d_handle *h);
 int  swe2d_turbine_rows_read(swe2d_handle *h, double *out, int32_t *n_rows);
 
+/* ---- Discrete tidal turbine farms (thetis/turbines.py:174-210): single turbines at coordinates, each a bump density
+ *     d(x) = sum_t psi((x - x_t)/r) psi((y - y_t)/r) / (r^2 1.45661),   psi(s) = |s| < 1 ? exp(1 - 1/(1 - s^2)) : 0,   r = D_proj/2,
+ * integrated with a rule of the caller's (n_q <= SWE2D_MAX_FARM_QUAD points; phi [n_q][nodes_per_cell] the basis functions at the
+ * points in the node order of the state, w [n_q] weights that sum to 1 on the reference cell).  A discrete farm takes a slot of the
+ * SWE2D_MAX_FARMS numbering and writes its power into the same rows as a continuous one, so swe2d_turbine_power, _power_limbs,
+ * _rows_* and swe2d_turbine_farm_clear serve both kinds, and the fused and dataflow kernels decline the handle in the same way.
+ * Its drag is not part of the stage kernels: after every stage launch one launch per discrete farm adds beta dt M^-1 R_farm(U_in)
+ * to the velocity of the stage's output, over the farm's own cell list (a handle whose only farms are discrete runs the stage
+ * kernel of a handle without farms).
+ * _set: xy [n_turbines][2] (n_turbines >= 0; turbines outside the mesh are legal), cell_mask [n_cells] non-zero = the cell belongs
+ * to the farm's subdomain.  The cell list - owned cells of the subdomain whose bounding box meets a turbine's square |x - x_t| < r,
+ * |y - y_t| < r - is built on the host, the density is tabulated on the device at the rule's points of the listed cells, summed
+ * over a cell's candidate turbines in the order of xy.  Not with wetting-drying (SWE2D_ERR_UNSUPPORTED); refused inside a stream
+ * capture.  On an allocation failure (SWE2D_ERR_HIP) the slot keeps what it held.
+ * _density_read: cells_out [n_list] the listed cells, density_out [n_q][n_list]; *n_list / *n_q are always set, the arrays may be
+ * null to ask for the sizes.
+ * _turbine_power: per turbine, int power * (the turbine's own bump) dx over the farm's cells, of the state in buffer A; each value
+ * a limb sum rounded once.  Overlapping bumps split the farm's power: the values add up to the farm's entry of
+ * swe2d_turbine_power up to rounding.  Synchronous. */
+#define SWE2D_MAX_FARM_QUAD 64
+int  swe2d_dfarm_set(swe2d_handle *h, int32_t farm, const swe2d_turbine_params *p, int32_t n_turbines, const double *xy,
+                     const uint8_t *cell_mask, int32_t n_q, const double *phi, const double *w);
+int  swe2d_dfarm_density_read(swe2d_handle *h, int32_t farm, int32_t *n_list, int32_t *n_q, int32_t *cells_out, double *density_out);
+int  swe2d_dfarm_turbine_power(swe2d_handle *h, int32_t farm, double *out);
+
 /* ---- Harmonic tidal elevation on open boundaries (thetis/forcing.py, TidalBoundaryForcing.set_tidal_field):
  *     eta_b(x, t) = mean(x) + sum_k amp_k(x) cos(omega_k t - phase_k(x))
  * evaluated on the device for the end nodes of the listed boundary facets, into the planes swe2d_set_bc_facets(h, 0, ...) writes

@@ -27,6 +27,7 @@ ABI_VERSION = 12         # include/swe2d.h SWE2D_ABI_VERSION
 OPT_COUNT = 15
 SNAPSHOT_SLOTS = 2
 MAX_FARMS, MAX_THRUST_TABLE = 8, 16   # include/swe2d.h SWE2D_MAX_FARMS, SWE2D_MAX_THRUST_TABLE
+MAX_FARM_QUAD = 64                    # include/swe2d.h SWE2D_MAX_FARM_QUAD
 MAX_TIDE_CONSTITUENTS = 32            # include/swe2d.h SWE2D_MAX_TIDE_CONSTITUENTS
 STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
 PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
@@ -209,6 +210,10 @@ SYMBOLS = {
     'swe2d_turbine_rows_reserve': (ctypes.c_int, [_H, ctypes.c_int32]),
     'swe2d_turbine_rows_append': (ctypes.c_int, [_H]),
     'swe2d_turbine_rows_read': (ctypes.c_int, [_H, _dp, _ip]),
+    'swe2d_dfarm_set': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.POINTER(TurbineParams), ctypes.c_int32, _dp,
+                                       ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32, _dp, _dp]),
+    'swe2d_dfarm_density_read': (ctypes.c_int, [_H, ctypes.c_int32, _ip, _ip, _ip, _dp]),
+    'swe2d_dfarm_turbine_power': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
     'swe2d_tide_set': (ctypes.c_int, [_H, ctypes.c_int32, _ip, _ip, ctypes.c_int32, _dp, _dp, _dp, _dp]),
     'swe2d_tide_clear': (ctypes.c_int, [_H]),
     'swe2d_tide_clock': (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int64]),

@@ -83,7 +83,7 @@ void fill_stage_args(Handle *h, SweStageArgs &a, int in, int u0, int out, double
     a.nu_v = h->nu_v; a.nu_const = h->nu_const;
     a.visc_sipg = 3.0*h->sipg_factor;
     a.visc_grad_div = h->visc_grad_div; a.visc_grad_depth = h->visc_grad_depth;
-    a.farms = h->n_farms > 0 ? h->farm_table : nullptr;
+    a.farms = h->n_cfarms > 0 ? h->farm_table : nullptr;
 }
 
 // Launch one stage on cells [c0, c1).  in/out/u0 are state buffer indices.
@@ -177,6 +177,8 @@ int launch_stage(Handle *h, int in, int u0, int out, double a0, double a1, doubl
             HIP_TRY(h, hipGetLastError());
         }
     }
+    // discrete turbine farms: U_out[uv] += beta*dt*M^-1 R_farm(U_in) over each farm's own cell list (swe2d_dfarm.hip)
+    if (h->n_farms > h->n_cfarms) return dfarm_launch_drag(h, in, out, beta, c0, c1);
     return SWE2D_OK;
 }
 

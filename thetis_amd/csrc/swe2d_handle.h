@@ -251,9 +251,21 @@ struct Handle {
         double *density = nullptr;                      // npc nodal planes, zero outside the farm's cells
         int *cells = nullptr;                           // owned cells with a non-zero density
         int n_list = 0;
+        // a discrete farm (swe2d_dfarm.hip): single turbines as bump densities, tabulated at the points of the farm's own rule over
+        // `cells` - here the owned cells of the subdomain whose bounding box meets a turbine's square.  `density` stays null.
+        bool discrete = false;
+        int n_q = 0, n_turbines = 0;                    // points of the rule, turbines
+        double radius = 0.0;                            // projected_diameter / 2
+        double *dtab = nullptr;                         // [n_q][n_list] density at the points of the listed cells
+        double *txy = nullptr;                          // [n_turbines][2] turbine coordinates
+        int *csr = nullptr;                             // c_off [n_list + 1] | c_idx [nnz] | t_off [n_turbines + 1] | t_pos [nnz]
+        int nnz = 0;                                    // (cell, candidate turbine) pairs
+        unsigned long long *tpow = nullptr;             // [n_turbines][SWE_SUM_LIMBS + 1] limb sums of swe2d_dfarm_turbine_power
+        double phi[SWE2D_MAX_FARM_QUAD*4] = {0.0}, w[SWE2D_MAX_FARM_QUAD] = {0.0};     // the rule (kernel arguments of the passes)
     };
     Farm farms[SWE2D_MAX_FARMS];
     int n_farms = 0;                                    // live slots
+    int n_cfarms = 0;                                   // ... of them continuous: the ones the stage kernels carry (SweStageArgs::farms)
     SweFarmTable *farm_table = nullptr;                 // the device's copy of the farms' constants (SweStageArgs::farms)
     int farm_blocks = 0;                                // blocks of a power launch
     unsigned long long *farm_rows = nullptr;            // [farm_rows_cap + 1][SWE_FARM_ROW] limb sums; the last row is swe2d_turbine_power's
@@ -342,7 +354,7 @@ inline RoctxRange::RoctxRange(const Handle *h, const char *name)
 inline bool has_sources(const Handle *h)
 {
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) return true;
-    if (h->n_farms > 0) return true;
+    if (h->n_cfarms > 0) return true;                  // (discrete farms are a pass of their own after the stage kernel)
     return h->scalar[SWE2D_SCALAR_LINEAR_DRAG] >= 0 || h->scalar[SWE2D_SCALAR_QUADRATIC_DRAG] >= 0
            || h->scalar[SWE2D_SCALAR_MANNING_DRAG] >= 0 || h->scalar[SWE2D_SCALAR_NIKURADSE] >= 0;
 }
@@ -407,6 +419,13 @@ size_t p2p_channel_offset(const int *width, int c, int n_recv);
 void probe_free_all(Handle *h);
 // ---- tidal turbine farms (swe2d_turbine.hip): frees every farm and the power rows (swe2d_destroy)
 void farm_free_all(Handle *h);
+bool farm_capturing(Handle *h);
+void farm_release(Handle::Farm &f);                     // frees what a slot holds, of either kind
+int farm_upload_table(Handle *h);                       // the device's copy of the farms' constants, after every change of a slot
+int farm_rows_alloc(Handle *h, int capacity);
+// ---- discrete turbine farms (swe2d_dfarm.hip)
+int dfarm_launch_drag(Handle *h, int in, int out, double beta, int c0, int c1);   // after a stage launch: U_out[uv] += beta*dt*M^-1 R_farm(U_in)
+int dfarm_launch_power(Handle *h, unsigned long long *row);                       // the discrete farms' power of buffer A into their slots of `row`
 // ---- harmonic tidal boundary elevation (swe2d_tide.hip)
 void tide_free(Handle *h);                              // frees the table (swe2d_destroy)
 int tide_launch(Handle *h, double t);                   // one launch: the boundary elevation at time t into the elevation planes of bc_field

@@ -88,9 +88,7 @@ __global__ void __launch_bounds__(SWE_BLOCK) swe_turbine_power_kernel(const SweF
     swe_sum_accumulate(P, row + (size_t)m*SWE_SUM_LIMBS, row + SWE_MAX_FARMS*SWE_SUM_LIMBS);
 }
 
-namespace {
-
-bool farm_capturing(Handle *h)
+bool swe2d_impl::farm_capturing(Handle *h)
 {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool yes = h->stream && hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
@@ -98,26 +96,33 @@ bool farm_capturing(Handle *h)
     return yes;
 }
 
-void farm_release(Handle::Farm &f)
+void swe2d_impl::farm_release(Handle::Farm &f)
 {
     if (f.density) (void)hipFree(f.density);
     if (f.cells) (void)hipFree(f.cells);
+    if (f.dtab) (void)hipFree(f.dtab);
+    if (f.txy) (void)hipFree(f.txy);
+    if (f.csr) (void)hipFree(f.csr);
+    if (f.tpow) (void)hipFree(f.tpow);
     f = Handle::Farm();
 }
 
 // the device's copy of the farms' constants, rebuilt after every change (the stream is idle: the callers synchronise first)
-int farm_upload_table(Handle *h)
+// A discrete slot has its constants in the table but is not live in it: the stage kernels and swe_turbine_power_kernel pass it by,
+// the passes of swe2d_dfarm.hip read f[m].
+int swe2d_impl::farm_upload_table(Handle *h)
 {
     SweFarmTable t{};
     int blocks = 0;
-    h->n_farms = 0;
+    h->n_farms = h->n_cfarms = 0;
     for (int m = 0; m < SWE2D_MAX_FARMS; m++) {
         const Handle::Farm &f = h->farms[m];
         if (!f.live) continue;
         h->n_farms++;
+        if (!f.discrete) h->n_cfarms++;
         const swe2d_turbine_params &p = f.par;
         SweFarm &d = t.f[m];
-        t.live[m] = 1;
+        t.live[m] = f.discrete ? 0 : 1;
         d.thrust_area_const = p.thrust_area_const;
         d.support_area = p.support_area;
         d.half_rho_area = 0.5*p.rho0*p.rotor_area;
@@ -132,7 +137,7 @@ int farm_upload_table(Handle *h)
         d.cells = f.cells;
         d.n_list = f.n_list;
         d.block0 = blocks;
-        blocks += (f.n_list + SWE_BLOCK - 1)/SWE_BLOCK;
+        if (!f.discrete) blocks += (f.n_list + SWE_BLOCK - 1)/SWE_BLOCK;
     }
     h->farm_blocks = blocks;
     if (!h->farm_table) HIP_TRY(h, hipMalloc(&h->farm_table, sizeof(SweFarmTable)));
@@ -140,7 +145,7 @@ int farm_upload_table(Handle *h)
     return SWE2D_OK;
 }
 
-int farm_rows_alloc(Handle *h, int capacity)
+int swe2d_impl::farm_rows_alloc(Handle *h, int capacity)
 {
     if (h->farm_rows && h->farm_rows_cap == capacity) return SWE2D_OK;
     if (h->farm_rows) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(h->farm_rows)); h->farm_rows = nullptr; }
@@ -150,9 +155,13 @@ int farm_rows_alloc(Handle *h, int capacity)
     return SWE2D_OK;
 }
 
-// one launch: the limb sums of every farm's power of the state in buffer A, added to `row` (zeroed by the caller)
+namespace {
+
+// one launch (and one per discrete farm): the limb sums of every farm's power of the state in buffer A, added to `row` (zeroed by
+// the caller)
 int launch_power(Handle *h, unsigned long long *row)
 {
+    if (h->n_farms > h->n_cfarms) { if (int rc = dfarm_launch_power(h, row)) return rc; }
     if (h->farm_blocks == 0) return SWE2D_OK;
     SWE_CHK_SYNC(h->stream);
     if (h->npc == 4)
@@ -170,7 +179,7 @@ int launch_power(Handle *h, unsigned long long *row)
 void swe2d_impl::farm_free_all(Handle *h)
 {
     for (auto &f : h->farms) farm_release(f);
-    h->n_farms = 0;
+    h->n_farms = h->n_cfarms = 0;
     if (h->farm_table) { (void)hipFree(h->farm_table); h->farm_table = nullptr; }
     if (h->farm_rows) { (void)hipFree(h->farm_rows); h->farm_rows = nullptr; }
 }
@@ -204,6 +213,7 @@ int swe2d_turbine_farm_set(swe2d_handle *hh, int32_t farm, const swe2d_turbine_p
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                          // launches that read the old table / density are done
     Handle::Farm &f = h->farms[farm];
+    if (f.discrete) farm_release(f);                                      // the slot changes its kind
     const size_t plane_bytes = (size_t)h->npc*h->stride*sizeof(double);
     if (!f.density) {
         HIP_TRY(h, hipMalloc(&f.density, plane_bytes));

@@ -661,6 +661,39 @@ class Swe2dDevice(object):
         self._ck(self.lib.swe2d_turbine_rows_read(self.h, _ptr(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
+    # -- discrete tidal turbine farms: csrc/swe2d_dfarm.hip
+    def dfarm_set(self, farm, params, xy, cell_mask, phi, w):
+        """farm slot ``farm`` as a discrete farm: ``params`` (_lib.TurbineParams), turbine coordinates ``xy`` (T, 2), the cells of
+        the farm's subdomain ``cell_mask`` (N,) bool, the farm's rule ``phi`` (n_q, k), ``w`` (n_q,) (function.farm_quadrature)"""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+        mask = np.asarray(cell_mask, dtype=bool).reshape(self.n_cells)
+        if self.perm is not None:
+            mask = mask[self.perm]
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        phi = np.ascontiguousarray(np.asarray(phi, dtype=np.float64).reshape(-1, self.npc))
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(len(phi)))
+        self._ck(self.lib.swe2d_dfarm_set(self.h, int(farm), ctypes.byref(params), len(xy), _ptr(xy) if len(xy) else None,
+                                          mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(phi), _ptr(phi), _ptr(w)))
+        self._dfarm_turbines = dict(getattr(self, '_dfarm_turbines', {}))
+        self._dfarm_turbines[int(farm)] = len(xy)
+
+    def dfarm_density_read(self, farm):
+        """(cells (L,) in the caller's numbering, density (n_q, L)): the listed cells of a discrete farm and the bump sum at the
+        rule's points of each"""
+        n, q = ctypes.c_int32(), ctypes.c_int32()
+        self._ck(self.lib.swe2d_dfarm_density_read(self.h, int(farm), ctypes.byref(n), ctypes.byref(q), None, None))
+        cells = np.zeros(max(n.value, 1), dtype=np.int32)
+        dens = np.zeros((q.value, max(n.value, 1)))
+        self._ck(self.lib.swe2d_dfarm_density_read(self.h, int(farm), ctypes.byref(n), ctypes.byref(q), _iptr(cells), _ptr(dens)))
+        cells = cells[:n.value].astype(np.int64)
+        return (cells if self.perm is None else np.asarray(self.perm)[cells]), dens[:, :n.value]
+
+    def dfarm_turbine_power(self, farm):
+        """power of every turbine of a discrete farm (T,), synchronously"""
+        out = np.zeros(max(getattr(self, '_dfarm_turbines', {}).get(int(farm), 0), 1))
+        self._ck(self.lib.swe2d_dfarm_turbine_power(self.h, int(farm), _ptr(out)))
+        return out[:getattr(self, '_dfarm_turbines', {}).get(int(farm), 0)]
+
     # -- harmonic tidal boundary elevation: csrc/swe2d_tide.hip
     def tide_set(self, slots, omegas, mean, amp, phase):
         """The tide table of the boundary facets of the marker slots ``slots``, in the order of ``boundary_facets`` slot after slot:

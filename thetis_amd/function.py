@@ -10,7 +10,7 @@ import numpy as np
 from .options import Constant
 
 __all__ = ['FunctionSpace', 'Function', 'MixedFunction', 'get_functionspace', 'triangle_quadrature',
-           'quadrilateral_quadrature', 'cell_quadrature']
+           'quadrilateral_quadrature', 'cell_quadrature', 'farm_quadrature', 'MAX_FARM_QUAD']
 
 # 6-point, degree-4 Dunavant rule (barycentric points, weights sum to 1)
 _a1, _b1, _w1 = 0.445948490915965, 0.108103018168070, 0.223381589678011
@@ -39,6 +39,42 @@ def quadrilateral_quadrature(n=2):
 
 def cell_quadrature(npc):
     return triangle_quadrature() if npc == 3 else quadrilateral_quadrature()
+
+
+MAX_FARM_QUAD = 64       # include/swe2d.h SWE2D_MAX_FARM_QUAD: points of a discrete farm's rule (kernel arguments of its passes)
+
+
+def farm_quadrature(npc, degree):
+    """The rule of a discrete turbine farm, ``dx(degree=quadrature_degree)`` of the reference: basis values phi (n_q, npc) in the
+    node order of the state and weights summing to 1 on the reference cell, exact for polynomials of total degree ``degree``.
+
+    Quadrilaterals: tensor Gauss-Legendre with degree//2 + 1 points per direction.  Triangles: the collapsed (Duffy) rule - the
+    point (s (1 - t), t) with weight w_s w_t (1 - t) of Gauss-Legendre rules on [0, 1] with degree//2 + 1 points in s and
+    (degree + 1)//2 + 1 in t (the factor 1 - t raises the t-degree by one).  Not FIAT's scheme of that degree: any rule exact to
+    the degree is a reading of ``dx(degree=...)``."""
+    degree = int(degree)
+    if degree < 0:
+        raise ValueError('quadrature_degree must be >= 0')
+    n_s = degree//2 + 1
+    n_t = n_s if npc == 4 else (degree + 1)//2 + 1
+    if n_s*n_t > MAX_FARM_QUAD:
+        raise NotImplementedError('quadrature_degree = {:d}: the rule has {:d} points, the device passes of a discrete farm take at '
+                                  'most SWE2D_MAX_FARM_QUAD = {:d}'.format(degree, n_s*n_t, MAX_FARM_QUAD))
+    if npc == 4:
+        return quadrilateral_quadrature(n_s)
+
+    def gauss01(n):
+        x, w = np.polynomial.legendre.leggauss(n)
+        return 0.5*(x + 1.0), 0.5*w
+    (xs, ws), (xt, wt) = gauss01(n_s), gauss01(n_t)
+    phi, w = [], []
+    for s, a in zip(xs, ws):
+        for t, b in zip(xt, wt):
+            x, y = s*(1 - t), t
+            phi.append([1 - x - y, x, y])
+            w.append(a*b*(1 - t))
+    w = np.array(w)
+    return np.array(phi), w/w.sum()
 
 
 class FunctionSpace(object):

@@ -302,8 +302,10 @@ class TidalTurbineFarmOptions(FrozenOptions):
 
 
 class DiscreteTidalTurbineFarmOptions(TidalTurbineFarmOptions):
-    """Discrete farm options (options.py:524-531).  Selectable for API fidelity; the device path raises for it (the bump
-    densities need the degree-10 rule of ``quadrature_degree``)."""
+    """Discrete farm options (options.py:524-531): ``turbine_coordinates`` pairs of floats or ``Constant``s, one bump density per
+    turbine (turbines.DiscreteTidalTurbineFarm).  ``quadrature_degree``: the degree to which the farm's own rule is exact
+    (function.farm_quadrature; up to 14, the 64 points of SWE2D_MAX_FARM_QUAD).  ``turbine_density`` is not read; a farm
+    without coordinates raises ``NotImplementedError`` when the equations are built."""
     name = 'Discrete Farm options'
     _spec = OrderedDict([
         ('turbine_coordinates', (list, _any)),

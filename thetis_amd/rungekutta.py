@@ -258,12 +258,18 @@ class ERKGenericShuOsher(TimeIntegrator):
         if self.comm is not None and self.comm.size > 1:
             raise NotImplementedError('tidal_turbine_farms on several ranks: the partitioned driver does not carry turbine farms yet '
                                       '(run the farm script on one device)')
-        if not hasattr(self.device, 'turbine_farm_set'):
+        from .turbines import DiscreteTidalTurbineFarm
+        if any(isinstance(farm, DiscreteTidalTurbineFarm) for farm in farms) and not hasattr(self.device, 'dfarm_set'):
+            raise NotImplementedError('discrete_tidal_turbine_farms: this device class has no discrete turbine farms')
+        if not all(isinstance(farm, DiscreteTidalTurbineFarm) for farm in farms) and not hasattr(self.device, 'turbine_farm_set'):
             raise NotImplementedError('tidal_turbine_farms: this device class has no turbine farms')
         for i, farm in enumerate(farms):
             sig = farm.density_signature()
             if self._farm_signatures.get(i) != sig:
-                self.device.turbine_farm_set(i, farm.device_params(), farm.density_nodal())
+                if isinstance(farm, DiscreteTidalTurbineFarm):
+                    self.device.dfarm_set(i, farm.device_params(), farm.coordinates, farm.cells, farm.phi, farm.w)
+                else:
+                    self.device.turbine_farm_set(i, farm.device_params(), farm.density_nodal())
                 self._farm_signatures[i] = sig
 
     def turbine_power(self):

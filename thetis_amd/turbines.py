@@ -4,7 +4,9 @@ Tidal turbine farms (thetis/turbines.py:17-171, 213-264): turbine types, ``Tidal
 The drag term and the power integral are evaluated on the device (csrc/swe2d_kernels.h: swe_farm_terms, csrc/swe2d_turbine.hip:
 swe_turbine_power_kernel); the classes here hold the parameters, state the same formulas in numpy for host-side use
 (``friction_coefficient``, ``number_of_turbines``) and hand the device what it needs (``device_params``, ``density_nodal``).
-Not here: the pyadjoint half of the reference's module (optimisation callback, distance constraints), discrete farms and the
+``DiscreteTidalTurbineFarm`` (turbines.py:174-210) places single turbines as bump densities; its drag is a pass of its own after
+each stage launch and its power, per farm and per turbine, is integrated with the farm's own rule (csrc/swe2d_dfarm.hip).
+Not here: the pyadjoint half of the reference's module (optimisation callback, distance constraints), moving turbines and the
 shear profile - each raises ``NotImplementedError`` naming the option.
 """
 import ctypes
@@ -15,12 +17,12 @@ import numpy as np
 
 from . import _lib
 from .callback import DiagnosticCallback
-from .function import Function, cell_quadrature
+from .function import Function, cell_quadrature, farm_quadrature
 from .options import Constant
 from .shallowwater_eq import physical_constants
 
-__all__ = ['TidalTurbine', 'ConstantThrustTurbine', 'TabulatedThrustTurbine', 'TidalTurbineFarm', 'TurbineFunctionalCallback',
-           'linearly_interpolate_table', 'farm_cells', 'build_farms']
+__all__ = ['TidalTurbine', 'ConstantThrustTurbine', 'TabulatedThrustTurbine', 'TidalTurbineFarm', 'DiscreteTidalTurbineFarm',
+           'TurbineFunctionalCallback', 'linearly_interpolate_table', 'farm_cells', 'build_farms', 'BUMP_NORM']
 
 
 def linearly_interpolate_table(x_list, y_list, y_final, x):
@@ -226,6 +228,84 @@ class TidalTurbineFarm(object):
         return p
 
 
+BUMP_NORM = 1.45661      # integral of the unit bump over its square, as the reference rounds it (turbines.py:210)
+
+
+def _bump(s):
+    """psi(s) = exp(1 - 1/(1 - s^2)) inside |s| < 1, zero at and beyond (turbines.py:201-208)"""
+    s = np.asarray(s, dtype=np.float64)
+    inside = np.abs(s) < 1.0
+    with np.errstate(divide='ignore', over='ignore', invalid='ignore'):
+        return np.where(inside, np.exp(1.0 - 1.0/(1.0 - np.where(inside, s, 0.0)**2)), 0.0)
+
+
+class DiscreteTidalTurbineFarm(TidalTurbineFarm):
+    """turbines.py:174-210: turbines at coordinates, each a bump of radius projected_diameter/2 that integrates to one turbine.
+    The density is not a Function here: the device tabulates it at the points of the farm's rule (``quadrature_degree``,
+    function.farm_quadrature) in the cells around the turbines, ``turbine_density`` states the same sum in numpy."""
+
+    def __init__(self, mesh, subdomain, options):
+        super().__init__(None, subdomain, options, mesh)
+        self.quadrature_degree = int(options.quadrature_degree)
+        self.phi, self.w = farm_quadrature(mesh.cells.shape[1], self.quadrature_degree)
+        self.radius = 0.5*self.turbine.projected_diameter
+        self.coordinates = np.zeros((0, 2))
+        self.turbine_density = self.density
+        self.add_turbines(options.turbine_coordinates)
+
+    def add_turbines(self, coordinates):
+        """append turbines at ``coordinates``: pairs of floats or ``Constant``s (turbines.py:189-199)"""
+        xy = np.array([[float(c) for c in pair] for pair in coordinates], dtype=np.float64).reshape(-1, 2)
+        if not np.isfinite(xy).all():
+            raise ValueError('turbine_coordinates must be finite')
+        self.coordinates = np.concatenate([self.coordinates, xy])
+
+    def density(self, xy):
+        """the bump sum at points ``xy`` (..., 2), turbine after turbine"""
+        xy = np.asarray(xy, dtype=np.float64)
+        r = self.radius
+        d = np.zeros(xy.shape[:-1])
+        for x_t, y_t in self.coordinates:
+            d = d + _bump((xy[..., 0] - x_t)/r)*_bump((xy[..., 1] - y_t)/r)/(r**2*BUMP_NORM)
+        return d
+
+    def density_signature(self):
+        return ('d', self.coordinates.tobytes(), self.quadrature_degree, self.radius)
+
+    def density_nodal(self):
+        raise NotImplementedError('a discrete farm has no nodal density: its bumps are tabulated at the points of its own rule')
+
+    def _cell_points(self):
+        """(N, q, 2) the rule's points in every cell (left to right, as the device forms them), (N, q) weight * det J"""
+        p = self.mesh.cell_xy()
+        pts = self.phi[None, :, 0, None]*p[:, None, 0, :]
+        for i in range(1, p.shape[1]):
+            pts = pts + self.phi[None, :, i, None]*p[:, None, i, :]
+        if p.shape[1] == 3:
+            jac = self.mesh.cell_areas()[:, None]*np.ones(len(self.w))
+        else:
+            a, b = p[:, 1] - p[:, 0], p[:, 3] - p[:, 0]
+            c = p[:, 0] - p[:, 1] + p[:, 2] - p[:, 3]
+            cross = lambda s, t: s[:, 0]*t[:, 1] - s[:, 1]*t[:, 0]       # noqa: E731
+            xi, ze = self.phi[:, 1] + self.phi[:, 2], self.phi[:, 2] + self.phi[:, 3]
+            jac = cross(a, b)[:, None] + cross(a, c)[:, None]*xi + cross(c, b)[:, None]*ze
+        return pts, jac*self.w
+
+    def number_of_turbines(self):
+        """int density dx(subdomain) with the farm's rule (close to, not exactly, the number of turbines placed: the bump is not a
+        polynomial, its norm has five digits, and a bump may reach beyond the subdomain)"""
+        pts, wj = self._cell_points()
+        return float((self.density(pts)*wj)[self.cells].sum())
+
+    def turbine_powers(self):
+        """power of every turbine, of the solver's current state, on the device"""
+        if self._solver is None:
+            raise RuntimeError('the farm is not attached to a solver (FlowSolver2d.create_equations builds the farms)')
+        stepper = _swe_stepper(self._solver)
+        stepper._sync_to_device()
+        return stepper.device.dfarm_turbine_power(self._index)
+
+
 def _swe_stepper(solver_obj):
     stepper = solver_obj.timestepper
     return getattr(stepper, 'swe', stepper)            # the coupled integrator (tracers) holds the shallow water stepper
@@ -233,10 +313,7 @@ def _swe_stepper(solver_obj):
 
 def build_farms(options, mesh):
     """``FlowSolver2d.tidal_farms``: the list of farms in the reference's order (solver2d.py:462-485), or None"""
-    if len(options.discrete_tidal_turbine_farms) > 0:
-        raise NotImplementedError('discrete_tidal_turbine_farms: bump densities need the degree-10 quadrature of '
-                                  'DiscreteTidalTurbineFarmOptions.quadrature_degree, which the device kernels do not have')
-    if len(options.tidal_turbine_farms) == 0:
+    if len(options.tidal_turbine_farms) + len(options.discrete_tidal_turbine_farms) == 0:
         return None
     farms = []
     for subdomain, farm_options_list in options.tidal_turbine_farms.items():
@@ -245,8 +322,24 @@ def build_farms(options, mesh):
                             'solver2d.FlowSolver2d(mesh2d, bathymetry_2d).options.tidal_turbine_farms[site_ID] = [farm_options]')
         for farm_options in farm_options_list:
             farms.append(TidalTurbineFarm(farm_options.turbine_density, subdomain, farm_options, mesh))
+    for subdomain, farm_options_list in options.discrete_tidal_turbine_farms.items():
+        if not isinstance(farm_options_list, list):
+            raise TypeError('Farm options must be entered as a list e.g. '
+                            'solver2d.FlowSolver2d(mesh2d, bathymetry_2d).options.discrete_tidal_turbine_farms[site_ID] = [farm_options]')
+        if farm_options_list and getattr(options, 'use_wetting_and_drying', False):
+            raise NotImplementedError('discrete_tidal_turbine_farms with use_wetting_and_drying: the discrete farms\' pass does not '
+                                      'carry the wetting-drying depth')
+        for farm_options in farm_options_list:
+            farm = DiscreteTidalTurbineFarm(mesh, subdomain, farm_options)
+            if len(farm.coordinates) == 0:
+                # (the reference builds such a farm for its optimisation workflow, which places and moves the turbines later)
+                raise NotImplementedError('discrete_tidal_turbine_farms: a farm without turbine_coordinates - turbines placed or '
+                                          'moved after the equations are built belong to the optimisation workflow, which is not '
+                                          'on the device path; give the coordinates in DiscreteTidalTurbineFarmOptions')
+            farms.append(farm)
     if len(farms) > _lib.MAX_FARMS:
-        raise NotImplementedError('tidal_turbine_farms: more than SWE2D_MAX_FARMS = {:d} farms'.format(_lib.MAX_FARMS))
+        raise NotImplementedError('tidal_turbine_farms: more than SWE2D_MAX_FARMS = {:d} farms (continuous and discrete '
+                                  'together)'.format(_lib.MAX_FARMS))
     return farms
 
 

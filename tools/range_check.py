@@ -26,10 +26,10 @@ def exercise():
         mesh, bath, uv, eta = case
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
-        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'tide', 'stats',
+        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'stats',
                         'stats+wetting-drying'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
-            bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') else bath)
+            bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') or variant == 'dfarm' else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
             markers = mesh.boundary_markers
             if variant == 'open+fields':
@@ -69,6 +69,25 @@ def exercise():
                 dens[-1] = 0.0                       # ... whose farm-cell list ends one short of the last cell
                 dev.turbine_farm_set(3, par2, dens)
                 assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
+            if variant == 'dfarm':
+                # discrete turbine farms (csrc/swe2d_dfarm.hip): the cell list, the CSR of candidate turbines and its transpose, the
+                # coordinates, the density table, the state planes and the mesh arrays are read and the output velocity is written
+                # through the checked accesses - by the density kernel at set-up, the drag pass after every stage launch of the
+                # advances below, the power pass and the per-turbine pass (rule and constants: kernel arguments / the SweFarmTable;
+                # limb sums: atomics on host-checked sizes).  One farm over the whole mesh with overlapping turbines, one outside
+                # and one clipped by the boundary; a second on half of the cells with the largest rule.
+                from thetis_amd.function import farm_quadrature
+                lo, hi = cxy.reshape(-1, 2).min(axis=0), cxy.reshape(-1, 2).max(axis=0)
+                span = hi - lo
+                par = _lib.TurbineParams()
+                par.rotor_area, par.projected_diameter, par.rho0, par.upwind_correction = 254.0, 0.3*span[1], 1000.0, 1
+                par.thrust_area_const, par.power_const, par.support_area = 0.8*254.0, 0.4, 5.0
+                txy = lo + span*np.array([[0.3, 0.4], [0.35, 0.5], [0.7, 0.02], [1.0, 1.0], [2.0, 0.5]])
+                dev.dfarm_set(1, par, txy, np.ones(mesh.num_cells, dtype=bool), *farm_quadrature(k, 10))
+                half = cxy[:, :, 0].mean(axis=1) > np.median(cxy[:, :, 0].mean(axis=1))
+                dev.dfarm_set(6, par, txy[:2] + 0.3*span*np.array([1.0, 0.0]), half, *farm_quadrature(k, 14))
+                assert len(dev.dfarm_density_read(1)[0]) > 0 and len(dev.dfarm_density_read(6)[0]) > 0
+                assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
             if variant == 'tide':
                 # harmonic tidal boundary elevation: swe_tide_kernel reads its table and the facet list and writes the elevation planes
                 # of the boundary fields through the checked accesses, one launch in front of every stage launch of the advances below
@@ -95,6 +114,16 @@ def exercise():
                 assert rows.shape[0] == 3 and np.isfinite(rows).all() and (rows[:, [0, 3]] >= 0).all() and rows[:, 3].min() > 0, rows
                 assert np.isfinite(dev.turbine_power()).all()
                 n_launch += 8
+            if variant == 'dfarm':
+                dev.turbine_rows_reserve(2)
+                for _ in range(2):
+                    dev.advance(1)
+                    dev.turbine_rows_append()
+                rows = dev.turbine_rows_read()
+                each = dev.dfarm_turbine_power(1)
+                assert rows.shape[0] == 2 and np.isfinite(rows).all() and rows[:, 1].min() > 0 and rows[:, 6].min() > 0, rows
+                assert each.shape == (5,) and np.isfinite(each).all() and each[4] == 0.0 and each[:2].min() > 0, each
+                n_launch += 12
             if variant.startswith('stats'):
                 # running field statistics: swe_stats_kernel reads the state planes (wetting-drying: also the cell vertices, alpha and the
                 # bathymetry) and read-modify-writes the accumulator planes of its set through the checked accesses; the weights are
