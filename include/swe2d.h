@@ -610,12 +610,50 @@ int  swe2d_tide_set(swe2d_handle *h, int32_t n_facets, const int32_t *cells, con
                     const double *omega, const double *mean, const double *amp, const double *phase);
 int  swe2d_tide_clear(swe2d_handle *h);
 /* The clock of the advances: step k of the next one starts at t_k = t_base + (double)(k_first + k)*dt - never an accumulated sum -,
- * its stage i is evaluated at t_k + c_i*dt, c = (0, 1, 1/2) (ForwardEuler: t_k + dt).  An advance of n steps adds n to k_first. */
+ * its stage i is evaluated at t_k + c_i*dt, c = (0, 1, 1/2) (ForwardEuler: t_k + dt).  An advance of n steps adds n to k_first.
+ * It is the handle's one clock: the atmospheric record below (swe2d_atm_*) is evaluated by it too, with or without a tide table, and
+ * it advances once per step whichever of the two is present. */
 int  swe2d_tide_clock(swe2d_handle *h, double t_base, int64_t k_first);
 /* One launch at an explicit time (asynchronous): what the step-by-step path calls before swe2d_solve_stage. */
 int  swe2d_tide_eval(swe2d_handle *h, double t);
 /* The values the elevation planes hold for the listed facets, out[n_facets][2].  Synchronous. */
 int  swe2d_tide_read(swe2d_handle *h, double *out);
+
+/* ---- Atmospheric forcing from a record of snapshots (thetis/forcing.py, AtmosphericForcingInterpolator.set_fields): 10 m wind and
+ * mean-sea-level pressure per mesh vertex at n_times instants, interpolated linearly in time and turned into wind stress,
+ *     x = (1 - alpha)*x_j + alpha*x_{j+1}  for u, v, p,     j the largest index with times[j] <= t (at most n_times - 2),
+ *     alpha = (t - times[j])/(times[j+1] - times[j])       (within 1e-6 outside [0, 1]: clamped; further out: SWE2D_ERR_INVALID_ARGUMENT)
+ *     m = sqrt(u*u + v*v),  tau = C_D(m)*SWE2D_ATM_RHO_AIR*m,  tau_x = tau*u,  tau_y = tau*v
+ *     LARGE_YEAGER_2009: C_D = 1e-3*(2.7/(m + 1e-3) + 0.142 + m/13.09 - 3.14807e-10*m6), m6 = (m*m)*(m*m)*(m*m); 2.34e-3 where m > 33
+ *     LARGE_POND_1981:   C_D = 1.2e-3; 1e-3*(0.49 + 0.065*m) where m > 11          SMITH_BANKE_1975: C_D = (0.63 + 0.066*m)/1000
+ * formed left to right without contraction, written into the planes of SWE2D_FIELD_WIND_STRESS and SWE2D_FIELD_ATMOSPHERIC_PRESSURE of
+ * every cell (the continuous P1 injection of swe2d_set_field_vertex).  A handle with a record steps like one with a tide table: stage
+ * launches, one evaluation launch in front of each (after the tide's, if any) at the time of the clock (swe2d_tide_clock), all enqueued
+ * by the one swe2d_advance / swe2d_advance_forward_euler / swe2d_advance_coupled call; the fused and the dataflow kernels decline it
+ * (the *_info calls and swe2d_flow_supported report 0; swe2d_solve_flow, swe2d_solve_step_cells, swe2d_solve_stage_pair_cells and
+ * per-launch swe2d_advance_timed return SWE2D_ERR_UNSUPPORTED).  An advance one of whose stage times lies outside the record fails
+ * with SWE2D_ERR_INVALID_ARGUMENT before anything is enqueued: the state and the clock are untouched.  The time is a kernel argument:
+ * inside a stream capture those advances and every swe2d_atm_* call return SWE2D_ERR_UNSUPPORTED.  No reference counterpart at the C
+ * level. */
+#define SWE2D_ATM_WIND 1
+#define SWE2D_ATM_PRESSURE 2
+#define SWE2D_ATM_LARGE_YEAGER_2009 0
+#define SWE2D_ATM_LARGE_POND_1981 1
+#define SWE2D_ATM_SMITH_BANKE_1975 2
+#define SWE2D_ATM_RHO_AIR 1.22
+/* Sets (or replaces) the record, all of it resident on the device: times[n_times] strictly increasing (n_times >= 2), wind_u, wind_v,
+ * pressure [n_times][n_vertices] in the numbering of swe2d_mesh.vertex_xy, all finite; `which` = SWE2D_ATM_WIND | SWE2D_ATM_PRESSURE
+ * names the quantities forced (the tables of the other may be NULL), `method` the stress formulation.  Allocates the planes of the
+ * forced fields if absent.  An allocation failure (SWE2D_ERR_HIP, the message names the bytes asked for) leaves the handle as it was. */
+int  swe2d_atm_set(swe2d_handle *h, int32_t n_times, const double *times, const double *wind_u, const double *wind_v,
+                   const double *pressure, int32_t method, int32_t which);
+/* Drops the record; the planes keep their last values (swe2d_set_field(h, field, NULL) frees them). */
+int  swe2d_atm_clear(swe2d_handle *h);
+/* One launch at an explicit time (asynchronous): what the step-by-step path calls before swe2d_solve_stage. */
+int  swe2d_atm_eval(swe2d_handle *h, double t);
+/* What the planes of the two fields hold, in the nodal layout of swe2d_set_field: wind_nodal[n_cells][nodes_per_cell][2],
+ * pressure_nodal[n_cells][nodes_per_cell]; either may be NULL.  Synchronous. */
+int  swe2d_atm_read(swe2d_handle *h, double *wind_nodal, double *pressure_nodal);
 
 /* ---- Running field statistics: extrema, means and harmonic sums of the whole state over every sampled step.
  * A statistics set holds 8 + 2K accumulators per DG node (K harmonic constituents, 0 <= K <= SWE2D_MAX_TIDE_CONSTITUENTS) in planes

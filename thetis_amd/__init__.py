@@ -20,7 +20,7 @@ from . import solver2d  # noqa: F401
 from .callback import DetectorsCallback, TimeSeriesCallback2D  # noqa: F401
 from .pointeval import PointNotInDomainError, select_and_move_detectors  # noqa: F401
 from .expr import *  # noqa: F401,F403  (SpatialCoordinate, conditional, as_vector, sin, cos, exp, sqrt, pi ...)
-from .forcing import HarmonicTidalForcing  # noqa: F401
+from .forcing import AtmosphericForcing, HarmonicTidalForcing, compute_wind_stress  # noqa: F401
 from .fieldstats import FieldStatisticsCallback  # noqa: F401
 from .function import Function, FunctionSpace, get_functionspace  # noqa: F401
 from .mesh import Mesh2d, PeriodicRectangleMesh, RectangleMesh, SquareMesh, UnitSquareMesh  # noqa: F401

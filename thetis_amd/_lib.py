@@ -29,6 +29,9 @@ SNAPSHOT_SLOTS = 2
 MAX_FARMS, MAX_THRUST_TABLE = 8, 16   # include/swe2d.h SWE2D_MAX_FARMS, SWE2D_MAX_THRUST_TABLE
 MAX_FARM_QUAD = 64                    # include/swe2d.h SWE2D_MAX_FARM_QUAD
 MAX_TIDE_CONSTITUENTS = 32            # include/swe2d.h SWE2D_MAX_TIDE_CONSTITUENTS
+ATM_WIND, ATM_PRESSURE = 1, 2         # include/swe2d.h SWE2D_ATM_*: the quantities of an atmospheric record
+ATM_METHODS = {'LargeYeager2009': 0, 'LargePond1981': 1, 'SmithBanke1975': 2}     # include/swe2d.h SWE2D_ATM_<formulation>
+ATM_RHO_AIR = 1.22                    # include/swe2d.h SWE2D_ATM_RHO_AIR
 STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
 PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
@@ -219,6 +222,10 @@ SYMBOLS = {
     'swe2d_tide_clock': (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int64]),
     'swe2d_tide_eval': (ctypes.c_int, [_H, ctypes.c_double]),
     'swe2d_tide_read': (ctypes.c_int, [_H, _dp]),
+    'swe2d_atm_set': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32]),
+    'swe2d_atm_clear': (ctypes.c_int, [_H]),
+    'swe2d_atm_eval': (ctypes.c_int, [_H, ctypes.c_double]),
+    'swe2d_atm_read': (ctypes.c_int, [_H, _dp, _dp]),
     'swe2d_stats_create': (ctypes.c_int, [_H, ctypes.c_int32, _ip]),
     'swe2d_stats_append': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
     'swe2d_stats_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64)]),

@@ -542,6 +542,7 @@ void swe2d_destroy(swe2d_handle *hh)
     probe_free_all(h);
     farm_free_all(h);
     tide_free(h);
+    atm_free(h);
     stats_free_all(h);
     for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
@@ -926,15 +927,17 @@ int swe2d_advance_forward_euler(swe2d_handle *hh, int n_steps)
     if (h->n_owned != h->n_cells) return fail(h, SWE2D_ERR_UNSUPPORTED, "ForwardEuler is not available on partitions");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
-    if (int rc = tide_refuse_capture(h)) return rc;
+    if (int rc = forcing_refuse_capture(h)) return rc;
+    if (int rc = atm_check_advance(h, n_steps, true)) return rc;          // (nothing is enqueued unless every time lies inside the record)
     for (int it = 0; it < n_steps; it++) {
-        // (a tide table: the boundary elevation of the NEW time first, timeintegrator.py:161-162)
+        // (a tide table, an atmospheric record: the forcing of the NEW time first, timeintegrator.py:161-162)
         if (h->tide.n > 0) { if (int rc = tide_launch(h, tide_stage_time(h, it, -1))) return rc; }
+        if (h->atm.n_t > 0) { if (int rc = atm_launch(h, tide_stage_time(h, it, -1))) return rc; }
         // U_new = U + dt M^-1 R(U): stage 0 of the Shu-Osher form; the result becomes buffer A by a pointer swap
         if (int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, 0, h->n_owned)) return rc;
         swap_state_buffers(h);                             // buffer B now holds the state before the step, not a stage solution
     }
-    if (h->tide.n > 0) h->tide.k_first += n_steps;
+    if (forced(h)) h->clock_k_first += n_steps;
     return SWE2D_OK;
 }
 
@@ -979,7 +982,7 @@ int swe2d_advance_timed(swe2d_handle *hh, int n_steps, int per_launch, float *ms
         if (ms_kernel_avg) *ms_kernel_avg = *ms_total/(3.0f*n_steps);
         return SWE2D_OK;
     }
-    if (h->tide.n > 0) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_advance_timed per launch: not with a tide table (time the whole advance)");
+    if (forced(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_advance_timed per launch: not with a tide table or an atmospheric record (time the whole advance)");
     // events around every launch of a step, on the launch stream: the launches step_swe makes (the mean is per element-update - a
     // third of a step - in every case)
     StepPath path;

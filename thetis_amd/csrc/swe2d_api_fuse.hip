@@ -276,8 +276,8 @@ int swe2d_solve_stage_pair_cells(swe2d_handle *hh, int32_t cell_end_0, int32_t c
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (cell_end_1 < 0 || cell_end_1 > cell_end_0 || cell_end_0 > h->n_cells) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "bad cell ranges");
-    // (two stages in one call: the second would see the boundary elevation of the first stage's time)
-    if (h->tide.n > 0) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_stage_pair_cells: not with a tide table (swe2d_tide_eval + swe2d_solve_stage_cells per stage)");
+    // (two stages in one call: the second would see the boundary elevation / the atmospheric fields of the first stage's time)
+    if (forced(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_solve_stage_pair_cells: not with a tide table or an atmospheric record (swe2d_tide_eval / swe2d_atm_eval + swe2d_solve_stage_cells per stage)");
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     StepPath path;

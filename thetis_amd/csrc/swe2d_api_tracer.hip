@@ -581,11 +581,13 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
     HIP_TRY(h, hipSetDevice(h->device));
     if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance_coupled");
+    // (nothing is enqueued unless every stage time of the call lies inside the atmospheric record)
+    if (!tracer_only) { if (int rc = atm_check_advance(h, n_steps, false)) return rc; }
     for (int it = 0; it < n_steps; it++) {
         // the shallow-water step as swe2d_advance makes it on a mesh beyond the dataflow kernel: fused stage pair + stage 3 where
         // that covers the handle (cfg 4 on 1 M triangles), stage launches otherwise
         if (!tracer_only) { if (int rc = step_swe(h, kWholeStep, 1)) return rc; }
-        else if (h->tide.n > 0) h->tide.k_first++;                       // (the tide clock counts the steps of this call either way)
+        else if (forced(h)) h->clock_k_first++;                          // (the forcings' clock counts the steps of this call either way)
         for (int id = 0; id < (int)h->tracers.size(); id++) {
             // without a diffusion pass behind it the last stage kernel also writes the cell means the limiter starts from
             const bool fuse_mean = use_limiter && !h->tracers[id].diff;

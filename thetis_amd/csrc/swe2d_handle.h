@@ -277,10 +277,18 @@ struct Handle {
         double *tab = nullptr;                          // mean [2n] | amp [K][2n] | phase [K][2n]
         int *list = nullptr;                            // device cells [n] | facets [n]
         double *out = nullptr;                          // [2n] staging of swe2d_tide_read
-        double t_base = 0.0;                            // swe2d_tide_clock: step k of the next advance starts at t_base + (k_first + k)*dt
-        long long k_first = 0;
     };
     Tide tide;
+    // atmospheric forcing (swe2d_atm.hip): n_t > 0 = the handle has a record of wind / pressure snapshots
+    struct Atm {
+        int n_t = 0, which = 0, method = 0, W = 0;      // snapshots, quantities (wind = 1 | pressure = 2), stress formulation, doubles per vertex
+        std::vector<double> times;                      // [n_t] the host's copy: the bracket of a time is found here (atm_launch)
+        double *tab = nullptr;                          // [n_t][n_vertices][W]: u, v | p | u, v, p of a vertex interleaved
+    };
+    Atm atm;
+    // the clock of the forcings (swe2d_tide_clock): step k of the next advance starts at clock_t_base + (clock_k_first + k)*dt
+    double clock_t_base = 0.0;
+    long long clock_k_first = 0;
     // running field statistics (swe2d_stats.hip): slot = statistics id; a destroyed set leaves an empty slot
     struct Stats {
         bool live = false;
@@ -361,6 +369,9 @@ inline bool has_sources(const Handle *h)
 
 inline int grid_for(int n) { return (n + 255)/256; }
 
+// a forcing the device evaluates in front of every stage launch, by the handle's clock: a tide table, an atmospheric record
+inline bool forced(const Handle *h) { return h->tide.n > 0 || h->atm.n_t > 0; }
+
 // options (swe2d_set_option): on unless switched off / the value in seconds with its default
 inline bool opt_on(const Handle *h, int o) { return h->opt[o] != 0; }
 inline double opt_seconds(const Handle *h, int o, double dflt) { return h->opt[o] > 0 ? 1e-3*h->opt[o] : dflt; }
@@ -430,7 +441,11 @@ int dfarm_launch_power(Handle *h, unsigned long long *row);                     
 void tide_free(Handle *h);                              // frees the table (swe2d_destroy)
 int tide_launch(Handle *h, double t);                   // one launch: the boundary elevation at time t into the elevation planes of bc_field
 double tide_stage_time(const Handle *h, int step, int i_stage);   // time of a stage of step `step` of the advance being enqueued (i_stage < 0: ForwardEuler)
-int tide_refuse_capture(Handle *h);                     // SWE2D_ERR_UNSUPPORTED where a handle with a tide is stepped inside a stream capture
+int forcing_refuse_capture(Handle *h);                  // SWE2D_ERR_UNSUPPORTED where a handle with a tide table or an atmospheric record is stepped inside a stream capture
+// ---- atmospheric forcing (swe2d_atm.hip)
+void atm_free(Handle *h);                               // frees the record (swe2d_destroy); the field planes are the handle's
+int atm_launch(Handle *h, double t);                    // one launch: wind stress and pressure at time t into their field planes
+int atm_check_advance(Handle *h, int n_steps, bool forward_euler);   // SWE2D_ERR_INVALID_ARGUMENT where a stage time of the advance leaves the record
 // ---- running field statistics (swe2d_stats.hip): frees every statistics set of the handle (swe2d_destroy)
 void stats_free_all(Handle *h);
 

@@ -18,6 +18,7 @@ unsigned step_kernels(const Handle *h)
     if (h->visc) k = 0;                                      // viscosity: a pass after each stage launch (swe2d_sipg.h)
     if (h->n_farms > 0) k = 0;                               // tidal turbine farms: the stage kernels carry the term (swe_source_terms<true>)
     if (h->tide.n > 0) k = 0;                                // tidal boundary table: one tide launch in front of every stage launch (step_swe)
+    if (h->atm.n_t > 0) k = 0;                               // atmospheric record: the fields change per stage, a fused launch reads them once
     if (h->opt[SWE2D_OPT_BND_INLINE] == 0) k = 0;            // the epilogue variant was asked for: stage kernels only
     if (h->h_nbr.empty()) k &= ~(kPair | kTriple);           // the tiles are cut from the host copy of the neighbour codes
     if (!h->flow_flag || !h->flow_ex) k &= ~kFlow;           // the dataflow kernel's tables (flow_build)
@@ -122,11 +123,11 @@ int step_launch(Handle *h, StepPath path, int i)
     return stage_on_range(h, i, 0, h->n_owned);
 }
 
-int tide_refuse_capture(Handle *h)
+int forcing_refuse_capture(Handle *h)
 {
     // the time is a kernel argument: a replay of the captured launches would repeat it
-    if (h->tide.n > 0 && stream_capturing(h))
-        return fail(h, SWE2D_ERR_UNSUPPORTED, "a handle with a tide table cannot be stepped inside a stream capture (the time is a kernel argument)");
+    if (forced(h) && stream_capturing(h))
+        return fail(h, SWE2D_ERR_UNSUPPORTED, "a handle with a tide table or an atmospheric record cannot be stepped inside a stream capture (the time is a kernel argument)");
     return SWE2D_OK;
 }
 
@@ -134,15 +135,19 @@ int step_swe(Handle *h, StepCaller who, int n_steps)
 {
     StepPath path;
     if (n_steps <= 0) return SWE2D_OK;
-    if (h->tide.n > 0) {
-        // stage launches, the boundary elevation of the stage's time in front of each; the clock moves on by the steps made
-        if (int rc = tide_refuse_capture(h)) return rc;
+    if (forced(h)) {
+        // stage launches, the boundary elevation and the atmospheric fields of the stage's time in front of each; the clock moves on
+        // by the steps made.  Nothing is enqueued unless every stage time lies inside the atmospheric record.
+        if (int rc = forcing_refuse_capture(h)) return rc;
+        if (int rc = atm_check_advance(h, n_steps, false)) return rc;
         for (int k = 0; k < n_steps; k++)
             for (int i = 0; i < 3; i++) {
-                if (int rc = tide_launch(h, tide_stage_time(h, k, i))) return rc;
+                const double t = tide_stage_time(h, k, i);
+                if (h->tide.n > 0) { if (int rc = tide_launch(h, t)) return rc; }
+                if (h->atm.n_t > 0) { if (int rc = atm_launch(h, t)) return rc; }
                 if (int rc = stage_on_range(h, i, 0, h->n_owned)) return rc;
             }
-        h->tide.k_first += n_steps;
+        h->clock_k_first += n_steps;
         return SWE2D_OK;
     }
     if (int rc = whole_step_path(h, who, &path)) return rc;

@@ -91,7 +91,7 @@ double swe2d_impl::tide_stage_time(const Handle *h, int step, int i_stage)
 #pragma clang fp contract(off)
     static const double c[3] = {0.0, 1.0, 0.5};
     const double dt = h->par.dt;
-    const double t_k = h->tide.t_base + (double)(h->tide.k_first + step)*dt;
+    const double t_k = h->clock_t_base + (double)(h->clock_k_first + step)*dt;
     return i_stage < 0 ? t_k + dt : t_k + c[i_stage]*dt;
 }
 
@@ -120,11 +120,8 @@ int swe2d_tide_set(swe2d_handle *hh, int32_t n_facets, const int32_t *cells, con
     for (size_t k = 0; k < K; k++) if (!std::isfinite(omega[k])) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tide_set: the table must be finite");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                          // launches that read the old table are done
-    const double t_base = h->tide.t_base;
-    const long long k_first = h->tide.k_first;
-    tide_release(h);
+    tide_release(h);                                                      // (the clock is the handle's: a new table keeps it)
     Handle::Tide &td = h->tide;
-    td.t_base = t_base; td.k_first = k_first;                             // a new table keeps the clock
     if (!h->bc_field[0]) {                                                // as swe2d_set_bc_facets
         const size_t bytes = (size_t)2*h->npc*h->stride*sizeof(double);
         HIP_TRY(h, hipMalloc(&h->bc_field[0], bytes));
@@ -162,8 +159,8 @@ int swe2d_tide_clock(swe2d_handle *hh, double t_base, int64_t k_first)
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
     if (!std::isfinite(t_base) || k_first < 0) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tide_clock: t_base must be finite and k_first >= 0");
-    h->tide.t_base = t_base;
-    h->tide.k_first = (long long)k_first;
+    h->clock_t_base = t_base;
+    h->clock_k_first = (long long)k_first;
     return SWE2D_OK;
 }
 

@@ -731,6 +731,47 @@ class Swe2dDevice(object):
         self._ck(self.lib.swe2d_tide_read(self.h, _ptr(out)))
         return out[:getattr(self, '_tide_n', 0)]
 
+    # -- atmospheric forcing: csrc/swe2d_atm.hip
+    def atm_set(self, times, wind_u=None, wind_v=None, pressure=None, method='LargeYeager2009'):
+        """The record of snapshots: ``times`` (n_t,), ``wind_u`` / ``wind_v`` and/or ``pressure`` (n_t, V) in the mesh's vertex
+        numbering; the quantities whose tables are given are forced.  All of it becomes resident on the device."""
+        tm = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        nv = self._keep[1].shape[0]
+        if (wind_u is None) != (wind_v is None):
+            raise ValueError('wind_u and wind_v come together')
+        which = (_lib.ATM_WIND if wind_u is not None else 0) | (_lib.ATM_PRESSURE if pressure is not None else 0)
+        if not which:
+            raise ValueError('a wind or a pressure table is required')
+        if method not in _lib.ATM_METHODS:
+            raise ValueError('unknown wind stress method {!r}'.format(method))
+
+        def table(a):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (len(tm), nv):
+                raise ValueError('an atmospheric table must have shape (n_t, n_vertices) = ({:d}, {:d}), got {:}'.format(len(tm), nv, a.shape))
+            if self._vperm is not None:
+                a = a[:, self._vperm]
+            return np.ascontiguousarray(a)
+        u, v, p = table(wind_u), table(wind_v), table(pressure)
+        self._ck(self.lib.swe2d_atm_set(self.h, len(tm), _ptr(tm), None if u is None else _ptr(u), None if v is None else _ptr(v),
+                                        None if p is None else _ptr(p), _lib.ATM_METHODS[method], which))
+
+    def atm_clear(self):
+        self._ck(self.lib.swe2d_atm_clear(self.h))
+
+    def atm_eval(self, t):
+        """one launch: wind stress and pressure of time ``t`` (enqueued; what the step-by-step path calls before ``solve_stage``)"""
+        self._ck(self.lib.swe2d_atm_eval(self.h, float(t)))
+
+    def atm_read(self, wind=True, pressure=True):
+        """what the planes of the two fields hold: (wind stress (N, k, 2) or None, pressure (N, k) or None), caller's cell numbering"""
+        w = np.empty((self.n_cells, self.npc, 2)) if wind else None
+        p = np.empty((self.n_cells, self.npc)) if pressure else None
+        self._ck(self.lib.swe2d_atm_read(self.h, None if w is None else _ptr(w), None if p is None else _ptr(p)))
+        return (None if w is None else self._nodal_out(w), None if p is None else self._nodal_out(p))
+
     # -- running field statistics: csrc/swe2d_stats.hip
     def stats_create(self, n_constituents=0):
         """A statistics set with ``n_constituents`` harmonic constituents (8 + 2K accumulators per DG node).  Returns its id."""

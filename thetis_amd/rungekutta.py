@@ -14,10 +14,10 @@ import numpy as np
 from . import _lib
 from .spmd import make_device
 from .device import TideValues
-from .forcing import HarmonicTidalForcing
+from .forcing import AtmosphericForcing, HarmonicTidalForcing
 from .function import Function
 from .options import Constant
-from .shallowwater_eq import g_grav
+from .shallowwater_eq import g_grav, physical_constants
 from .timeintegrator import StepConsumer, TimeIntegrator
 
 __all__ = ['ForwardEuler', 'SSPRK33Abstract', 'ERKGenericShuOsher', 'SSPRK33', 'butcher_to_shuosher_form', 'advance_with_rows']
@@ -157,6 +157,10 @@ class ERKGenericShuOsher(TimeIntegrator):
         self._device_tide = None
         self._device_tide_signature = None
         self._host_tides = []
+        # an AtmosphericForcing given as options.wind_stress / options.atmospheric_pressure (_push_atm): likewise
+        self._device_atm = None
+        self._device_atm_signature = None
+        self._host_atm = None
         if equation.depth.use_wetting_and_drying:
             alpha = equation.depth.wetting_and_drying_alpha
             if isinstance(alpha, Function):
@@ -197,6 +201,8 @@ class ERKGenericShuOsher(TimeIntegrator):
         """Changes when a coefficient may have changed: Functions carry a host version, Constants their value."""
         if isinstance(v, Function):
             return ('f', id(v), v._host_version)
+        if isinstance(v, AtmosphericForcing):    # (the field planes are _push_atm's business: the device's own launches or set_fields)
+            return ('a', id(v))
         if v is None or callable(v):
             return ('o', id(v))
         return ('c', _const_value(v))
@@ -209,9 +215,17 @@ class ERKGenericShuOsher(TimeIntegrator):
         dev = self.device
         seen = getattr(self, '_field_signatures', {}) if only_changed else {}
         new = {}
+        self._push_atm()
+
+        def value(key):
+            """an AtmosphericForcing the HOST evaluates per stage stands for the field its ``set_fields`` writes"""
+            v = f.get(key)
+            if isinstance(v, AtmosphericForcing) and self._device_atm is None:
+                return v.wind_stress_field if key == 'wind_stress' else v.atm_pressure_field
+            return v
 
         def changed(key):
-            new[key] = self._signature(f.get(key))
+            new[key] = self._signature(value(key))
             return seen.get(key) != new[key]
         if not only_changed:
             dev.set_scalar(_lib.SCALAR_NORM_SMOOTHER, float(getattr(self.equation.options, 'norm_smoother', 0.0) or 0.0))
@@ -236,8 +250,7 @@ class ERKGenericShuOsher(TimeIntegrator):
                               ('wind_stress', _lib.FIELD_WIND_STRESS, True)):
             if not changed(key):
                 continue
-            v = f.get(key)
-            self._set_field(fid, v, vector=vec)
+            self._set_field(fid, value(key), vector=vec)
         if changed('viscosity_h'):
             nu = f.get('viscosity_h')
             if nu is not None:                   # HorizontalViscosityTerm, shallowwater_eq.py:554-616
@@ -281,6 +294,8 @@ class ERKGenericShuOsher(TimeIntegrator):
     def _set_field(self, fid, v, vector=False):
         """Upload one coefficient field; a continuous (CG-P1) Function goes as one value per vertex and is injected into the
         DG nodes on the device (the cheap path for forcing fields that ``update_forcings`` changes every step)."""
+        if isinstance(v, AtmosphericForcing):
+            return                               # the device writes these planes itself (_push_atm: atm_set allocated them)
         if v is None:
             self.device.set_field(fid, None)
         elif isinstance(v, Function) and v.function_space().family == 'CG' and v.function_space().vector == vector:
@@ -388,29 +403,71 @@ class ERKGenericShuOsher(TimeIntegrator):
             self._device_tide, self._device_tide_signature = None, None
         return on_device
 
+    def _push_atm(self):
+        """Find the AtmosphericForcing among the option values and hand its record to the device (again only when the object or its
+        table signature changes).  Where the device cannot evaluate it - a device class without ``atm_set``, several ranks -
+        ``_host_atm`` is the object whose ``set_fields`` runs on the host in front of every stage, the fields going up per vertex."""
+        f = self.fields
+        found = []
+        for key, field, bit in (('wind_stress', 'wind_stress_field', _lib.ATM_WIND),
+                                ('atmospheric_pressure', 'atm_pressure_field', _lib.ATM_PRESSURE)):
+            v = f.get(key)
+            if isinstance(v, AtmosphericForcing):
+                if getattr(v, field) is None:
+                    raise ValueError("the AtmosphericForcing under options.{:} has no {:}".format(key, field))
+                if v.mesh is not self.equation.mesh:
+                    raise ValueError('the AtmosphericForcing under options.{:} lives on another mesh'.format(key))
+                found.append((v, bit))
+        if len(found) == 2 and found[0][0] is not found[1][0]:
+            raise NotImplementedError('two AtmosphericForcing objects on one solver: the device holds one atmospheric record; give '
+                                      'options.wind_stress and options.atmospheric_pressure the same object')
+        several_ranks = self.comm is not None and self.comm.size > 1
+        on_device = bool(found) and hasattr(self.device, 'atm_set') and not several_ranks
+        obj = found[0][0] if found else None
+        self._host_atm = None if on_device else obj
+        if on_device:
+            which = sum(bit for _, bit in found)
+            if float(physical_constants['rho_air']) != _lib.ATM_RHO_AIR:
+                raise NotImplementedError('the device evaluates the wind stress with rho_air = {:}'.format(_lib.ATM_RHO_AIR))
+            sig = obj.table_signature() + (which,)
+            if sig != self._device_atm_signature:
+                wind = bool(which & _lib.ATM_WIND)
+                self.device.atm_set(obj.times, obj.wind_u if wind else None, obj.wind_v if wind else None,
+                                    obj.pressure if which & _lib.ATM_PRESSURE else None, method=obj.method)
+                self._device_atm_signature = sig
+            self._device_atm = obj
+        elif self._device_atm is not None:
+            self.device.atm_clear()
+            self._device_atm, self._device_atm_signature = None, None
+
     @property
     def forced_per_stage(self):
         """a forcing the HOST evaluates in front of every stage even without ``update_forcings``: no batched steps"""
-        return bool(self._host_tides)
+        return bool(self._host_tides) or self._host_atm is not None
 
     @property
     def wants_clock(self):
-        """the device evaluates a tide: ``advance_steps`` takes the time loop's ``clock=(t_start, n_done)``"""
-        return self._device_tide is not None
+        """the device evaluates a tide or an atmospheric record: ``advance_steps`` takes the time loop's ``clock=(t_start, n_done)``"""
+        return self._device_tide is not None or self._device_atm is not None
 
     def _tide_clock(self, t_base, k_first=0):
-        if self._device_tide is not None:
+        if self.wants_clock:
             self.device.tide_clock(t_base, k_first)
 
     def _stage_forcings(self, t_stage, update_forcings, eval_tide=True):
-        """what precedes a stage evaluated at ``t_stage``: the tide, then the user's ``update_forcings``, then the uploads"""
+        """what precedes a stage evaluated at ``t_stage``: the tide and the atmospheric fields, then the user's ``update_forcings``,
+        then the uploads"""
         if eval_tide and self._device_tide is not None:
             self.device.tide_eval(t_stage)
+        if eval_tide and self._device_atm is not None:
+            self.device.atm_eval(t_stage)
         for f in self._host_tides:
             f.set_tidal_field(t_stage)
+        if self._host_atm is not None:
+            self._host_atm.set_fields(t_stage)
         if update_forcings is not None:
             update_forcings(t_stage)
-        if update_forcings is not None or self._host_tides:
+        if update_forcings is not None or self.forced_per_stage:
             self._push_bcs()
             self._push_fields(only_changed=True)
 
@@ -463,7 +520,7 @@ class ERKGenericShuOsher(TimeIntegrator):
 
     def advance(self, t, update_forcings=None):
         """Advances equations for one time step (rungekutta.py:949-952)."""
-        if update_forcings is None and not self._host_tides:
+        if update_forcings is None and not self.forced_per_stage:
             self._sync_to_device()
             self._tide_clock(t)
             self.device.advance(1)

@@ -19,7 +19,7 @@ from .options import Constant
 __all__ = ['ShallowWaterEquations', 'DepthExpression', 'g_grav', 'rho_0', 'physical_constants']
 
 # thetis/physical_constants.py:6-11: Constants, so that tests can re-assign them (test/swe2d/test_rossby_wave.py:154-155)
-physical_constants = {'g_grav': Constant(9.81), 'rho0': Constant(1000.0), 'von_karman': Constant(0.4)}
+physical_constants = {'g_grav': Constant(9.81), 'rho0': Constant(1000.0), 'von_karman': Constant(0.4), 'rho_air': Constant(1.22)}
 g_grav = physical_constants['g_grav']
 rho_0 = physical_constants['rho0']
 

@@ -26,7 +26,7 @@ def exercise():
         mesh, bath, uv, eta = case
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
-        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'stats',
+        for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'atm', 'stats',
                         'stats+wetting-drying'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
             bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') or variant == 'dfarm' else bath)
@@ -102,6 +102,25 @@ def exercise():
                 dev.tide_clock(1000.0, 7)
                 dev.tide_eval(44714.1)
                 assert dev.tide_read().shape == (nf, 2) and np.isfinite(dev.tide_read()).all()
+                assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
+                n_launch += 12
+            if variant == 'atm':
+                # atmospheric record: swe_atm_kernel reads cv and two snapshots of the record and writes the wind-stress and pressure
+                # planes of every cell through the checked accesses, one launch in front of every stage launch of the advances below.
+                # A record with one quantity alone (1 and 2 doubles per vertex), then with wind and pressure (3), each evaluated
+                # at the first, an interior and the last snapshot time.
+                rng = np.random.default_rng(8)
+                tm = np.array([0.0, 0.4, 1.7, 2.0, 6.5])
+                wu, wv = 30.0*rng.normal(size=(2, len(tm), mesh.num_vertices))
+                pa = 101325.0 + 500.0*rng.normal(size=(len(tm), mesh.num_vertices))
+                for tabs in ((None, None, pa), (wu, wv, None), (wu, wv, pa)):
+                    dev.atm_set(tm, *tabs)
+                    for t_eval in (tm[0], tm[2], tm[-1]):
+                        dev.atm_eval(t_eval)
+                    w_read, p_read = dev.atm_read(wind=tabs[0] is not None, pressure=tabs[2] is not None)
+                    assert all(a is None or np.isfinite(a).all() for a in (w_read, p_read))
+                    n_launch += 3
+                dev.tide_clock(0.0, 2)
                 assert dev.flow_supported() == 0 and not dev.fused_pair_info()[0]
                 n_launch += 12
             dev.set_state(0.1*uv, 0.1*np.abs(eta))
