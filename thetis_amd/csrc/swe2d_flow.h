@@ -52,8 +52,8 @@
 // whole mesh throughout.  After the launch state buffer 0 holds what the stage launches would have left there; buffers 1, 2
 // (the intermediate stage solutions) are not written.
 //
-// The arithmetic is that of swe_stage_kernel<NONLIN, LF, ., SRC, false, false, true(BINL)>, operation for operation and under
-// the same `fp contract(off)`: bit for bit the result of the stage launches on the same ranges (tests/test_gpu_flow_kernel.py).
+// The arithmetic of a cell is swe2d_tri.h's, the functions swe_stage_kernel calls: bit for bit the result of the stage launches on the
+// same ranges (tests/test_gpu_flow_kernel.py).
 #pragma once
 #include "swe2d_kernels.h"
 #include "swe2d_p2p.h"
@@ -234,49 +234,12 @@ __device__ __forceinline__ bool swe_flow_arrived(swe_u32x4 g, unsigned need)
 #endif
 }
 
-// right-hand side integrals of one cell: cell integrals + interior facet fluxes (boundary facets contribute zero here, their
-// flux is evaluated from the cell's own values and discarded - the branch-free facet loop of swe_stage_kernel).  The six traces
-// of facet f are read from LDS where the flux is formed: tr[f] = the LDS addresses (in doubles from `lds`) of {u, v, e at the
-// neighbour's node on my node f + 1; u, v, e at its node on my node f} - the block's own stage values for a neighbour inside
-// the block (a boundary facet points at this cell itself), the incoming staging entry for a rim facet.
-// Lines as in swe_stage_kernel, same order.
-// WD (wetting-drying, round 5): e[] is the elevation recovered from the displaced depth D the planes hold, Dn[] that depth = the
-// nodal total depth (swe_stage_kernel<..., WD>)
-template <bool NONLIN, bool WD = false>
-__device__ __forceinline__ void swe_flow_rhs_cell(const SweStageArgs &p, const double u[3], const double v[3], const double e[3],
-                                                  const double h[3], const double nx[3], const double ny[3], double bu[3], double bv[3],
-                                                  double be[3], const double *Dn = nullptr)
-{
-#pragma clang fp contract(off)
-    const double g = p.g;
-    double H[3], gxs[3], gys[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        H[i] = WD ? Dn[i] : (NONLIN ? h[i] + e[i] : h[i]);
-        gxs[i] = -0.5*nx[(i + 1) % 3];                     // A*grad(phi_i) = -nF_{i+1}/2
-        gys[i] = -0.5*ny[(i + 1) % 3];
-    }
-    const double ge3 = g*(e[0] + e[1] + e[2])*(1.0/3.0);
-    const double SHu = swe_int2(H, u)*(1.0/12.0), SHv = swe_int2(H, v)*(1.0/12.0);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        bu[i] = gxs[i]*ge3;
-        bv[i] = gys[i]*ge3;
-        be[i] = swe_dot2(gxs[i], SHu, gys[i], SHv);
-    }
-    if (NONLIN) {
-        const double Suu = swe_int2(u, u)*(1.0/12.0), Suv = swe_int2(u, v)*(1.0/12.0), Svv = swe_int2(v, v)*(1.0/12.0);
-        const double D12 = fma(gys[2], v[2], fma(gys[1], v[1], fma(gys[0], v[0],
-                           fma(gxs[2], u[2], fma(gxs[1], u[1], gxs[0]*u[0])))))*(1.0/12.0);
-        const double us = u[0] + u[1] + u[2], vs = v[0] + v[1] + v[2];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            bu[i] = fma(gys[i], Suv, fma(gxs[i], Suu, fma(D12, us + u[i], bu[i])));
-            bv[i] = fma(gys[i], Svv, fma(gxs[i], Suv, fma(D12, vs + v[i], bv[i])));
-        }
-    }
-}
-
+// The interior facets of one cell for the kernels that keep their traces in LDS: the six traces of facet f are read where the flux
+// is formed (swe_tri_facet).  tr[f] = the LDS addresses (in doubles from `lds`) of {u, v, e at the neighbour's node on my node f + 1;
+// u, v, e at its node on my node f} - the block's own stage values for a neighbour inside the block (a boundary facet points at
+// this cell itself), the incoming staging entry for a rim facet.  Then the source terms, if any.
+// e[]: the elevation; WD (wetting-drying): recovered from the displaced depth D the planes and the traces hold, Dn[] that depth of the
+// own nodes = the nodal total depth.
 // NTR = 3: tr[f][c] holds the two addresses of component c; NTR = 1 (the variants with source terms, which have no registers to
 // spare: 28 B/lane of scratch with the exchange inside, round 4-5): only component 0's pair is kept, the others follow from it -
 // the components of a trace are 1 apart in the staging area (a rim facet: address >= SWE_FLOW_XG) and 3*64 apart in the block's own
@@ -287,10 +250,7 @@ __device__ __forceinline__ void swe_flow_rhs_cell(const SweStageArgs &p, const d
 // (GEOM: what becomes of the facet lengths, pure functions of the mesh - SWE_GEOM_COMPUTE: evaluated here, every caller but the
 //  three-stage kernel of swe2d_fuse.h; SWE_GEOM_KEEP: evaluated here and left in the lane's LDS record, geo[f*PLANE] = Lf and
 //  geo[(3 + f)*PLANE] = 1/Lf of facet f; SWE_GEOM_STORED: taken from the record a SWE_GEOM_KEEP call filled - the values that
-//  instruction sequence gave, so the same bits.  swe_flow_finish: geo[6*PLANE] = 1/twoA in the same way)
-#define SWE_GEOM_COMPUTE 0
-#define SWE_GEOM_KEEP 1
-#define SWE_GEOM_STORED 2
+//  instruction sequence gave, so the same bits; SWE_GEOM_* are defined in swe2d_tri.h, whose finish treats 1/twoA in the same way)
 template <bool NONLIN, bool LF, bool SRC, int NTR, bool WD = false, int XG = SWE_FLOW_XG, int PLANE = SWE_BLOCK, int NLDS = SWE_FLOW_LDS_DOUBLES,
           int GEOM = SWE_GEOM_COMPUTE>
 __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k, const double u[3], const double v[3], const double e[3],
@@ -299,11 +259,9 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
                                                     double be[3], const double *Dn = nullptr, const double *al = nullptr, double *geo = nullptr)
 {
 #pragma clang fp contract(off)
-    const double g = p.g;
 #pragma unroll
     for (int f = 0; f < 3; f++) {
         const int a = f, b = (f + 1) % 3;
-        const bool bnd = ((bmarkers >> (8*f)) & 0xff) != 0;
         // tr[f][c] = address of component c (u, v, e) at the neighbour's node on my node f + 1 | the same on my node f << 16
         const unsigned ab0 = tr[f][0] & 0xffffu, aa0 = tr[f][0] >> 16;
         const unsigned step = ab0 >= (unsigned)XG ? 1u : (unsigned)(3*PLANE);
@@ -312,101 +270,20 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
         const double unb = lds[SWE_LDSI(ab0, NLDS)], una = lds[SWE_LDSI(aa0, NLDS)];
         const double vnb = lds[SWE_LDSI(ab1, NLDS)], vna = lds[SWE_LDSI(aa1, NLDS)];
         const double enb = lds[SWE_LDSI(ab2, NLDS)], ena = lds[SWE_LDSI(aa2, NLDS)];
-        const double nxs = nx[f], nys = ny[f];
         double Lf, rLf;
         if constexpr (GEOM == SWE_GEOM_STORED) { Lf = geo[f*PLANE]; rLf = geo[(3 + f)*PLANE]; }
-        else swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), Lf, rLf);
+        else swe_tri_facet_len(nx[f], ny[f], Lf, rLf);
         if constexpr (GEOM == SWE_GEOM_KEEP) { geo[f*PLANE] = Lf; geo[(3 + f)*PLANE] = rLf; }
-        double Fau, Fbu, Fav, Fbv, Fae, Fbe;
-        if constexpr (WD) {
-            // the neighbour's traces carry its nodal depth D; its elevation by the closed form (bathymetry and alpha are continuous)
-            const double ena_ = swe_wd_eta(ena, h[a], al[a]), enb_ = swe_wd_eta(enb, h[b], al[b]);
-            swe_facet_flux<NONLIN, LF, true>(g, p.sigma_lf, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b], Dn[a], Dn[b], una, unb, vna, vnb,
-                                             ena_, enb_, ena, enb, nxs, nys, Lf, rLf, Fau, Fbu, Fav, Fbv, Fae, Fbe);
-        } else
-        swe_facet_flux<NONLIN, LF, false>(g, p.sigma_lf, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b], 0.0, 0.0, una, unb, vna, vnb, ena, enb,
-                                          0.0, 0.0, nxs, nys, Lf, rLf, Fau, Fbu, Fav, Fbv, Fae, Fbe);
-        if (bnd) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }
-        bu[a] = fma(-0.5, Fau, bu[a]); bu[b] = fma(-0.5, Fbu, bu[b]);
-        bv[a] = fma(-0.5, Fav, bv[a]); bv[b] = fma(-0.5, Fbv, bv[b]);
-        be[a] = fma(-0.5, Fae, be[a]); be[b] = fma(-0.5, Fbe, be[b]);
+        swe_tri_facet<NONLIN, LF, WD>(p.g, p.sigma_lf, ((bmarkers >> (8*f)) & 0xff) != 0, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b],
+                                      WD ? Dn[a] : 0.0, WD ? Dn[b] : 0.0, WD ? al[a] : 0.0, WD ? al[b] : 0.0, una, unb, vna, vnb, ena, enb,
+                                      nx[f], ny[f], Lf, rLf, bu[a], bu[b], bv[a], bv[b], be[a], be[b]);
     }
     if (SRC) {
         double H[3], gxs[3], gys[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            H[i] = WD ? Dn[i] : (NONLIN ? h[i] + e[i] : h[i]);
-            gxs[i] = -0.5*nx[(i + 1) % 3];
-            gys[i] = -0.5*ny[(i + 1) % 3];
-        }
+        swe_tri_depths<NONLIN, WD>(h, e, Dn, H);
+        swe_tri_grad(nx, ny, gxs, gys);
         swe_source_terms(p, k, p.stride, twoA, u, v, H, gxs, gys, bu, bv, be);
     }
-}
-
-// mass inverse, Shu-Osher combine and the boundary facets of the cell (the BINL pass of swe_stage_kernel)
-// (WALLFAST: the closed-wall path of swe_boundary_facet; not in the variants with source terms - no registers to spare, 68 B of scratch)
-template <bool NONLIN, bool LF, bool WALLFAST, bool WD = false, int GEOM = SWE_GEOM_COMPUTE, int PLANE = SWE_BLOCK>
-__device__ __forceinline__ void swe_flow_finish(const SweStageArgs &p, int k, double beta, const double u[3], const double v[3],
-                                                const double e[3], const double h[3], const double nx[3], const double ny[3],
-                                                double twoA, int bmarkers, int bkind1, const double bu[3], const double bv[3], const double be[3],
-                                                const double wu[3], const double wv[3], const double we[3], double ou[3],
-                                                double ov[3], double oe[3], const double *Dn = nullptr, const double *al = nullptr,
-                                                double *geo = nullptr)
-{
-#pragma clang fp contract(off)
-    const double dtb6 = 6.0*p.dt*beta;
-    double rA;
-    if constexpr (GEOM == SWE_GEOM_STORED) rA = geo[6*PLANE];
-    else rA = swe_rcp(twoA);
-    if constexpr (GEOM == SWE_GEOM_KEEP) geo[6*PLANE] = rA;
-    const double s = dtb6*rA;
-    const double su = bu[0] + bu[1] + bu[2], sv = bv[0] + bv[1] + bv[2], se = be[0] + be[1] + be[2];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        ou[i] = fma(s, fma(4.0, bu[i], -su), wu[i]);
-        ov[i] = fma(s, fma(4.0, bv[i], -sv), wv[i]);
-        oe[i] = fma(s, fma(4.0, be[i], -se), we[i]);
-    }
-    if (bmarkers != 0) {
-        const double sfac = 6.0*p.dt*beta*swe_rcp(fma(-ny[0], -nx[2], -(nx[0]*ny[2])));
-        int rem = ((bmarkers & 0xff) ? 1 : 0) | ((bmarkers & 0xff00) ? 2 : 0) | ((bmarkers & 0xff0000) ? 4 : 0);
-        int kind_next = bkind1;
-        // scalars, not the parameter arrays: a select between loads through a pointer parameter becomes a load from a selected
-        // address and the arrays end up in scratch
-        const double u_0 = u[0], u_1 = u[1], u_2 = u[2], v_0 = v[0], v_1 = v[1], v_2 = v[2], e_0 = e[0], e_1 = e[1], e_2 = e[2];
-        const double h_0 = h[0], h_1 = h[1], h_2 = h[2], nx_0 = nx[0], nx_1 = nx[1], nx_2 = nx[2], ny_0 = ny[0], ny_1 = ny[1], ny_2 = ny[2];
-        const double D_0 = WD ? Dn[0] : 0.0, D_1 = WD ? Dn[1] : 0.0, D_2 = WD ? Dn[2] : 0.0;
-        const double al_0 = WD ? al[0] : 0.0, al_1 = WD ? al[1] : 0.0, al_2 = WD ? al[2] : 0.0;
-#define SWE_SEL3(x, i) ((i) == 0 ? x##_0 : ((i) == 1 ? x##_1 : x##_2))
-#pragma unroll 1
-        while (rem) {
-            const int f = (rem & 1) ? 0 : ((rem & 2) ? 1 : 2);
-            rem &= rem - 1;
-            const int a = f, b = (f == 2) ? 0 : f + 1;
-            const double nxs = SWE_SEL3(nx, f), nys = SWE_SEL3(ny, f);
-            double Lf, rLf;
-            swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), Lf, rLf);
-            double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
-            const double Ha_ = WD ? SWE_SEL3(D, a) : (!NONLIN ? SWE_SEL3(h, a) : SWE_SEL3(h, a) + SWE_SEL3(e, a));
-            const double Hb_ = WD ? SWE_SEL3(D, b) : (!NONLIN ? SWE_SEL3(h, b) : SWE_SEL3(h, b) + SWE_SEL3(e, b));
-            swe_boundary_facet<NONLIN, LF, WD, WALLFAST>(p, (bmarkers >> (8*f)) & 0xff, k, a, b, SWE_SEL3(u, a), SWE_SEL3(u, b), SWE_SEL3(v, a),
-                                                  SWE_SEL3(v, b), SWE_SEL3(e, a), SWE_SEL3(e, b), SWE_SEL3(h, a), SWE_SEL3(h, b),
-                                                  Ha_, Hb_, WD ? SWE_SEL3(al, a) : 0.0, WD ? SWE_SEL3(al, b) : 0.0, nxs, nys, Lf, rLf, Fau, Fbu, Fav,
-                                                  Fbv, Fae, Fbe, kind_next);
-            kind_next = -1;
-            const double dau = -0.5*Fau, dbu = -0.5*Fbu, dav = -0.5*Fav, dbv = -0.5*Fbv, dae = -0.5*Fae, dbe = -0.5*Fbe;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const double wa = (i == a) ? 3.0 : -1.0, wb = (i == b) ? 3.0 : -1.0;
-                ou[i] = fma(sfac, fma(wa, dau, wb*dbu), ou[i]);
-                ov[i] = fma(sfac, fma(wa, dav, wb*dbv), ov[i]);
-                oe[i] = fma(sfac, fma(wa, dae, wb*dbe), oe[i]);
-            }
-        }
-#undef SWE_SEL3
-    }
-    // zeta = D - h -> the limited depth D the device carries; dry-ground relaxation of the velocity (swe_stage_kernel<..., WD>)
-    if constexpr (WD) swe_wd_finish<3>(p.g, beta*p.dt, h, al, ou, ov, oe, !p.wd_skip_relax);
 }
 
 #ifdef SWE_WAVE_TIMING
@@ -440,8 +317,8 @@ __device__ __forceinline__ void swe_flow_finish(const SweStageArgs &p, int k, do
 // on tiles (padding granules still read), ... with three (profiles/r05s_flow_block_order.txt, r05t_flow_poll6.txt).
 // WD (round 5): wetting-drying.  The "elevation" values of the block - registers, LDS planes, rim granules, U(0), the exchange records -
 // are the displaced depth D the state planes hold; the elevation is recovered per stage (own nodes before the wave starts to wait,
-// the neighbours' where the fluxes are formed), the stage ends with swe_wd_finish: swe_stage_kernel<true, LF, ., SRC, true>'s
-// operations.  alpha of the cell's vertices stays in registers with the rest of the geometry.
+// the neighbours' where the fluxes are formed), the stage ends with swe_wd_finish.  alpha of the cell's vertices stays in registers
+// with the rest of the geometry.
 template <bool NONLIN, bool LF, bool SRC, bool FX, int POLL = 6, bool WD = false>
 __global__ __launch_bounds__(SWE_BLOCK) SWE_FLOW_OCCUPANCY void swe_flow_kernel(const SweFlowArgs q)
 {
@@ -747,14 +624,17 @@ SWE_FLOW_PUBLISH_STORES(pc_)                                                    
             // The cell integrals need no neighbour: they are evaluated BEFORE the wave starts to wait for its rim granules (it would
             // sleep in the polling loop otherwise), which takes them - a quarter of a stage's arithmetic - off the chain
             // "neighbour publishes -> this block sees it -> computes -> publishes" that sets the period of a stage (round 5).
-            // Same operations in the same order as before: the same bits.
             double bu[3], bv[3], be[3];
             const double twoA = fma(nx[0], ny[1], -(ny[0]*nx[1]));
             // wetting-drying: e[] holds D; the elevation of the own nodes (three reciprocals) is formed here, before the wait
             double eta[3];
 #pragma unroll
             for (int i = 0; i < 3; i++) eta[i] = WD ? swe_wd_eta(e[i], h[i], al[i]) : e[i];
-#define SWE_FLOW_CELL_TERMS_HERE swe_flow_rhs_cell<NONLIN, WD>(p, u, v, eta, h, nx, ny, bu, bv, be, e)
+#define SWE_FLOW_CELL_TERMS_HERE do {                                                                                                 \
+                double H[3];                                                                                                      \
+                swe_tri_depths<NONLIN, WD>(h, eta, e, H);                                                                         \
+                swe_tri_cell<NONLIN>(p.g, u, v, eta, H, nx, ny, bu, bv, be);                                                      \
+            } while (0)
             // w = a0*U(0) + a1*U_in: the first stage of a step has no U(0) term (swe_stage_kernel<., ., HASU0 = false>); with
             // wetting-drying the continuity equation advances zeta = D - h (the planes, U(0)'s too, hold D)
 #define SWE_FLOW_W_HERE do {                                                                                                          \
@@ -864,7 +744,8 @@ SWE_FLOW_PUBLISH_STORES(pc_)                                                    
             // (a lane outside the stage's range has no boundary facets to do: the outermost ghost layer of a partition, which is in no
             //  stage's range, points its missing neighbours at a wall - unmasked, every block that holds such a cell ran the boundary
             //  pass in every stage, +0.8 us for the 300 blocks next to the cuts of a rank of eight)
-            swe_flow_finish<NONLIN, LF, SWE_FLOW_WALLFAST_SRC || !SRC, WD>(p, k, q.beta[i3], u, v, eta, h, nx, ny, twoA, act ? bmarkers : 0, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe, e, al);
+            swe_tri_finish<NONLIN, LF, WD, SWE_FLOW_WALLFAST_SRC || !SRC>(p, k, q.beta[i3], twoA, u, v, eta, h, e, al, nx, ny, act ? bmarkers : 0, bkind1,
+                                                                          bu, bv, be, wu, wv, we, true, ou, ov, oe);
 #ifdef SWE_WAVE_TIMING
             if (ou[0] == 1.2345e300) return;          // the arithmetic has to be finished before the time stamp
             SWE_FT(3);

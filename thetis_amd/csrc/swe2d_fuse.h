@@ -9,9 +9,9 @@
 // the results go to LDS, and stage 2 is evaluated for the interior cells with every neighbour trace from LDS.  Per interior
 // cell the launch reads U(0) once (x 1.24 for the ring on the bench mesh) and writes U(2): 192 MB per launch at 1 M cells by the
 // counters where the two stage launches move 428 MB.
-// The arithmetic is the dataflow kernel's (swe_flow_rhs_cell / swe_flow_rhs_facets / swe_flow_finish = swe_stage_kernel's
-// operations in its order): bit for bit the stage launches (tests/test_gpu_parity.py::test_fused_stage_pair_gives_the_bits_...),
-// and checked directly against the oracle (::test_fused_stage_pair_matches_the_c_restatement...).
+// The arithmetic of a cell is swe2d_tri.h's, the functions swe_stage_kernel calls (the traces come from LDS: swe_flow_rhs_facets):
+// bit for bit the stage launches (tests/test_gpu_parity.py::test_fused_stage_pair_gives_the_bits_...), and checked directly against
+// the oracle (::test_fused_stage_pair_matches_the_c_restatement...).
 // Covers: triangles, whole mesh or the owned + ghost ranges of a partition, with or without source terms; no wetting-drying, no
 // viscosity (those keep the stage launches).
 #pragma once
@@ -139,11 +139,14 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
     if (real) {
         twoA = fma(nx[0], ny[1], -(ny[0]*nx[1]));
         double bu[3], bv[3], be[3], wu[3], wv[3], we[3];
-        swe_flow_rhs_cell<NONLIN>(p, u, v, e, h, nx, ny, bu, bv, be);
+        double H[3];
+        swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
+        swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
         swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE_XG, SWE_FUSE_WG, SWE_FUSE_LDS>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
-        swe_flow_finish<NONLIN, LF, true>(p, k, q.beta1, u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, o1u, o1v, o1e);
+        swe_tri_finish<NONLIN, LF, false, true>(p, k, q.beta1, twoA, u, v, e, h, nullptr, nullptr, nx, ny, bmarkers, bkind1, bu, bv, be,
+                                                wu, wv, we, true, o1u, o1v, o1e);
     }
     __syncthreads();                                       // every lane has read its traces of U(0)
     if (real) {
@@ -170,11 +173,14 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
         for (int f = 0; f < 3; f++) asm volatile("" : "+v"(tr[f][0]));
         asm volatile("" : "+v"(bmarkers), "+v"(twoA));
         double bu[3], bv[3], be[3], wu[3], wv[3], we[3], ou[3], ov[3], oe[3];
-        swe_flow_rhs_cell<NONLIN>(p, o1u, o1v, o1e, h, nx, ny, bu, bv, be);
+        double H[3];
+        swe_tri_depths<NONLIN, false>(h, o1e, nullptr, H);
+        swe_tri_cell<NONLIN>(p.g, o1u, o1v, o1e, H, nx, ny, bu, bv, be);
         swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE_XG, SWE_FUSE_WG, SWE_FUSE_LDS>(p, k, o1u, o1v, o1e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = lw[i][lane]; wv[i] = lw[3 + i][lane]; we[i] = lw[6 + i][lane]; }
-        swe_flow_finish<NONLIN, LF, true>(p, k, q.beta2, o1u, o1v, o1e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe);
+        swe_tri_finish<NONLIN, LF, false, true>(p, k, q.beta2, twoA, o1u, o1v, o1e, h, nullptr, nullptr, nx, ny, bmarkers, bkind1, bu, bv, be,
+                                                wu, wv, we, true, ou, ov, oe);
         const swe_rsrc_t gou = swe_rsrc(q.out), gov = swe_rsrc(q.out + 3*S), goe = swe_rsrc(q.out + 6*S);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -193,7 +199,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 // a tile reads ring cells whose owners may already have finished - and the host swaps the two pointers after the launch.
 // LDS: P0 [9][256] = U(0) (traces of stage 1; every lane's own U(0) for the Shu-Osher weights of stages 2 and 3), P1 [9][256] = the
 // running stage values (U(1), then U(2)), then the staging area of the traces from outside the tile: 36.9 KB + 6 x 8 B per slot.
-// Same arithmetic, same order as the stage launches: the same bits (tests/test_gpu_parity.py::test_fused_stage_triple...).
+// The arithmetic of a cell is swe2d_tri.h's: the bits of the stage launches (tests/test_gpu_parity.py::test_fused_stage_triple...).
 //
 // Roles and lanes (round 10).  The ROLES of a tile are numbered [interior | ring 1 | ring 2 | padding]; role r sits on the physical
 // lane (r + 64*rot) & 255, rot in 0..3 per tile, kept in counts[tile].y >> 16 (swe2d_tiles.h: SWE_FUSE3_ROT).  Stage 2 runs the roles
@@ -327,13 +333,15 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     if (real) {
         twoA = fma(nx[0], ny[1], -(ny[0]*nx[1]));
         double bu[3], bv[3], be[3], wu[3], wv[3], we[3], ou[3], ov[3], oe[3];
-        swe_flow_rhs_cell<NONLIN>(p, u, v, e, h, nx, ny, bu, bv, be);
+        double H[3];
+        swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
+        swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
         swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                      nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
-        swe_flow_finish<NONLIN, LF, true, false, GEOM1, SWE_FUSE_WG>(p, k, q.beta[0], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe,
-                                                        nullptr, nullptr, G);
+        swe_tri_finish<NONLIN, LF, false, true, GEOM1, SWE_FUSE_WG>(p, k, q.beta[0], twoA, u, v, e, h, nullptr, nullptr, nx, ny, bmarkers, bkind1,
+                                                                    bu, bv, be, wu, wv, we, true, ou, ov, oe, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { u[i] = ou[i]; v[i] = ov[i]; e[i] = oe[i]; }
     }
@@ -363,7 +371,9 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             asm volatile("" : "+v"(bmarkers));
             if (SRC || !SWE_FUSE3_GEOM) asm volatile("" : "+v"(twoA));     // (else nothing reads it after stage 1)
             double bu[3], bv[3], be[3], wu[3], wv[3], we[3];
-            swe_flow_rhs_cell<NONLIN>(p, u, v, e, h, nx, ny, bu, bv, be);
+            double H[3];
+            swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
+            swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
             swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                           nullptr, nullptr, G);
             const double a0 = q.a0[s], a1 = q.a1[s];
@@ -373,8 +383,8 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
                 wv[i] = fma(a0, lds[(3 + i)*SWE_FUSE_WG + lane], a1*v[i]);
                 we[i] = fma(a0, lds[(6 + i)*SWE_FUSE_WG + lane], a1*e[i]);
             }
-            swe_flow_finish<NONLIN, LF, true, false, GEOM23, SWE_FUSE_WG>(p, k, q.beta[s], u, v, e, h, nx, ny, twoA, bmarkers, bkind1, bu, bv, be, wu, wv, we, ou, ov, oe,
-                                                                          nullptr, nullptr, G);
+            swe_tri_finish<NONLIN, LF, false, true, GEOM23, SWE_FUSE_WG>(p, k, q.beta[s], twoA, u, v, e, h, nullptr, nullptr, nx, ny, bmarkers,
+                                                                         bkind1, bu, bv, be, wu, wv, we, true, ou, ov, oe, G);
         }
         if (s == 1) {
             __syncthreads();                               // every lane has read its traces of U(1)

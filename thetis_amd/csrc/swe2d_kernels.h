@@ -926,6 +926,8 @@ __device__ __forceinline__ void swe_source_terms(const SweStageArgs &p, int k, s
     }
 }
 
+#include "swe2d_tri.h"
+
 // Boundary facets (walls, open boundaries, boundary drag) are < 0.3 % of the work but their code needs ~60 registers of
 // temporaries.  In the TRIANGLE kernel they are therefore not evaluated inside the facet loop (which treats them as zero)
 // but in this epilogue, which runs for cells with a boundary facet after the rest of the cell update is finished - when
@@ -967,25 +969,14 @@ __device__ __forceinline__ void swe_boundary_epilogue(const SweStageArgs &p, int
         const double va_ = p.uin[(size_t)(3 + a)*S + k], vb_ = p.uin[(size_t)(3 + b)*S + k];
         const double da_ = p.uin[(size_t)(6 + a)*S + k], db_ = p.uin[(size_t)(6 + b)*S + k];      // eta, or D with wetting-drying
         const double ea = WD ? swe_wd_eta(da_, ha, ala) : da_, eb = WD ? swe_wd_eta(db_, hb, alb) : db_;
-        const double Ha = WD ? da_ : (NONLIN ? ha + ea : ha);
-        const double Hb = WD ? db_ : (NONLIN ? hb + eb : hb);
+        const double Ha = swe_tri_depth<NONLIN, WD>(ha, ea, da_), Hb = swe_tri_depth<NONLIN, WD>(hb, eb, db_);
         const double nxs = yb_ - ya_, nys = xa_ - xb_;
         double L, rL;
-        swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), L, rL);
+        swe_tri_facet_len(nxs, nys, L, rL);
         double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
         swe_boundary_facet<NONLIN, LF, WD>(p, -nbf, k, a, b, ua, ub, va_, vb_, ea, eb, ha, hb, Ha, Hb, ala, alb, nxs, nys,
                                            L, rL, Fau, Fbu, Fav, Fbv, Fae, Fbe);
-        const double dau = -0.5*Fau, dbu = -0.5*Fbu, dav = -0.5*Fav, dbv = -0.5*Fbv, dae = -0.5*Fae, dbe = -0.5*Fbe;
-        // M^-1 of a vector that is non-zero at nodes a and b only (4 d_i - (d_a + d_b)), static output indices
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const double wa = (i == a) ? 3.0 : -1.0, wb = (i == b) ? 3.0 : -1.0;
-            // explicit fma: the inline-boundary variant of the stage kernel repeats these lines with compile-time wa, wb and
-            // must round identically (left to the compiler, constant weights contract differently from run-time ones)
-            ou[i] = fma(sfac, fma(wa, dau, wb*dbu), ou[i]);
-            ov[i] = fma(sfac, fma(wa, dav, wb*dbv), ov[i]);
-            oe[i] = fma(sfac, fma(wa, dae, wb*dbe), oe[i]);
-        }
+        swe_tri_boundary_correct(sfac, a, b, Fau, Fbu, Fav, Fbv, Fae, Fbe, ou, ov, oe);
     }
 }
 
@@ -1137,11 +1128,9 @@ __device__ unsigned long long swe_wave_ts[6][SWE_WT_MAX];
 #define SWE_WT_DRAIN()
 #endif
 
-// BINL: boundary fluxes are evaluated after the cell's outputs are finished from the values the lane still holds (one pass per
-// lane over ITS boundary facet), instead of reloading the facet's nodes in swe_boundary_epilogue: no dependent memory round
-// trips in the waves that own boundary cells (a quarter of the waves of a 125 k-cell partition, and the last to finish).
-// 164-166 VGPRs, no scratch, 3 waves/SIMD (the boundary markers travel packed in one register, h + eta is re-formed).
-// Same bits as the epilogue path (tests/test_gpu_parity.py).
+// BINL: the boundary pass of swe_tri_finish (boundary facets from the values the lane still holds) instead of swe_boundary_epilogue,
+// which reloads the facet's nodes: no dependent memory round trips in the waves that own boundary cells (a quarter of the waves of
+// a 125 k-cell partition, and the last to finish).  Same bits either way (tests/test_gpu_parity.py).
 template <bool NONLIN, bool LF, bool HASU0, bool SRC, bool WD, bool VISC = false, bool BINL = false, bool LDSX = false>
 __global__ __launch_bounds__(SWE_BLOCK, SWE_MIN_WAVES) void swe_stage_kernel(const SweStageArgs p)
 {
@@ -1297,7 +1286,7 @@ __global__ __launch_bounds__(SWE_BLOCK, SWE_MIN_WAVES) void swe_stage_kernel(con
             we[i] = p.a1*(H[i] - h[i]);
             if (HASU0) we[i] = fma(p.a0, e0[i] - h[i], we[i]);
             e[i] = swe_wd_eta(H[i], h[i], al[i]);
-        } else H[i] = NONLIN ? h[i] + e[i] : h[i];
+        } else H[i] = swe_tri_depth<NONLIN, false>(h[i], e[i], 0.0);
     }
     SWE_WT_DRAIN();
     SWE_WT(2);
@@ -1310,26 +1299,37 @@ __global__ __launch_bounds__(SWE_BLOCK, SWE_MIN_WAVES) void swe_stage_kernel(con
         ny[f] = px[f] - px[b];
     }
     const double twoA = fma(nx[0], ny[1], -(ny[0]*nx[1]));
-    // A*grad(phi_i) = -nF_{i+1}/2
-    double gxs[3], gys[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        gxs[i] = -0.5*nx[(i + 1) % 3];
-        gys[i] = -0.5*ny[(i + 1) % 3];
-    }
 
-    // ---- cell integrals (closed form)
+    // The instances with the viscosity fused in (VISC) keep a LOCAL COPY of the cell integrals, the facet loop and the mass inverse
+    // instead of calling swe2d_tri.h.  swe_visc_interior is compiled with floating-point contraction allowed; which product of
+    // a sum the compiler fuses there follows the instructions around it, and with the shared functions around it 154 of 6.7 M
+    // values of the viscosity cases moved in their last bit; with the text below there is none (both runs:
+    // profiles/r14b_tri_same_bits.txt).  The copy relies on this kernel's own `fp contract(off)`.  These kernels have one launch
+    // path, so no cross-path promise depends on the copy; it goes when swe_visc_interior is pinned with explicit fmas under
+    // `fp contract(off)` - a change of bits, to be made on its own.
+    static_assert(!VISC || (!WD && !BINL), "the fused viscosity has no wetting-drying and no inline boundary pass");
     double bu[3], bv[3], be[3];
-    {
+    double Lf[3] = {0.0, 0.0, 0.0}, rLf[3] = {0.0, 0.0, 0.0};     // kept for the fused viscosity only
+    double ou[3], ov[3], oe[3];
+    // zeta = D - h -> limited depth D (stored); dry-ground relaxation.  (Not for the parity hook swe2d_tendency, a0 = a1 = 0: it
+    // returns the raw tendencies of (u, v, zeta).)
+    const bool wd_fin = WD && !(p.a0 == 0.0 && p.a1 == 0.0);
+    double gxs[3], gys[3];
+    if constexpr (VISC) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            gxs[i] = -0.5*nx[(i + 1) % 3];
+            gys[i] = -0.5*ny[(i + 1) % 3];
+        }
         const double ge3 = g*(e[0] + e[1] + e[2])*(1.0/3.0);
         const double SHu = swe_int2(H, u)*(1.0/12.0), SHv = swe_int2(H, v)*(1.0/12.0);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            bu[i] = gxs[i]*ge3;                              // +g eta div(psi)       shallowwater_eq.py:361
+            bu[i] = gxs[i]*ge3;
             bv[i] = gys[i]*ge3;
-            be[i] = swe_dot2(gxs[i], SHu, gys[i], SHv);      // +grad(phi).(H u)      shallowwater_eq.py:422
+            be[i] = swe_dot2(gxs[i], SHu, gys[i], SHv);
         }
-        if (NONLIN) {                                        // +(psi div u + u.grad psi).u  shallowwater_eq.py:478
+        if (NONLIN) {
             const double Suu = swe_int2(u, u)*(1.0/12.0), Suv = swe_int2(u, v)*(1.0/12.0),
                          Svv = swe_int2(v, v)*(1.0/12.0);
             const double D12 = fma(gys[2], v[2], fma(gys[1], v[1], fma(gys[0], v[0],
@@ -1341,103 +1341,68 @@ __global__ __launch_bounds__(SWE_BLOCK, SWE_MIN_WAVES) void swe_stage_kernel(con
                 bv[i] = fma(gys[i], Svv, fma(gxs[i], Suv, fma(D12, vs + v[i], bv[i])));
             }
         }
+    } else {
+        swe_tri_grad(nx, ny, gxs, gys);
+        swe_tri_cell<NONLIN>(g, u, v, e, H, nx, ny, bu, bv, be);
     }
-
-    // ---- facet integrals: 2-point Gauss-Legendre, numerical fluxes seen from this cell
-    double Lf[3] = {0.0, 0.0, 0.0}, rLf[3] = {0.0, 0.0, 0.0};     // kept for the fused viscosity only
 #pragma unroll
     for (int f = 0; f < 3; f++) {
         const int a = f, b = (f + 1) % 3;
-        const double nxs = nx[f], nys = ny[f];
-        const double len2 = swe_dot2(nxs, nxs, nys, nys);
-        double L, rL;
-        swe_sqrt_rsqrt(len2, L, rL);
-        if (VISC) { Lf[f] = L; rLf[f] = rL; }
-        double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
-        // Branch-free: a boundary facet carries this cell's own values as "neighbour" traces (finite numbers), its flux is
-        // evaluated like any other and discarded below.  With `if (nb[f] >= 0)` around this block the compiler sank the six
-        // trace loads of a facet into the branch - a third dependent trip to memory in every wave.  (The fused-viscosity variant
-        // keeps the branch: its traces stay live for swe_visc_interior and the branch-free form needs 256 VGPRs = 1 wave/SIMD,
-        // 248 instead of 185-198 us/step at 1 M cells.)
-        if (!(VISC || WD) || nb[f] >= 0) {
-            // neighbour's nodal depth on this facet: what its planes hold; its elevation by the closed form (bathymetry and alpha
-            // are continuous: same vertices)
-            const double Dna = WD ? ena[f] : 0.0, Dnb = WD ? enb[f] : 0.0;
-            const double ena_ = WD ? swe_wd_eta(Dna, h[a], al[a]) : ena[f], enb_ = WD ? swe_wd_eta(Dnb, h[b], al[b]) : enb[f];
-            swe_facet_flux<NONLIN, LF, WD>(g, p.sigma_lf, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b], H[a], H[b], una[f], unb[f],
-                                           vna[f], vnb[f], ena_, enb_, Dna, Dnb, nxs, nys, L, rL, Fau, Fbu, Fav, Fbv, Fae, Fbe);
+        if constexpr (VISC) {
+            const double nxs = nx[f], nys = ny[f];
+            const double len2 = swe_dot2(nxs, nxs, nys, nys);
+            double L, rL;
+            swe_sqrt_rsqrt(len2, L, rL);
+            Lf[f] = L; rLf[f] = rL;
+            double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
+            if (nb[f] >= 0)
+                swe_facet_flux<NONLIN, LF, false>(g, p.sigma_lf, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b], H[a], H[b], una[f], unb[f],
+                                                  vna[f], vnb[f], ena[f], enb[f], 0.0, 0.0, nxs, nys, L, rL, Fau, Fbu, Fav, Fbv, Fae, Fbe);
+            if (nb[f] < 0) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }
+            bu[a] = fma(-0.5, Fau, bu[a]); bu[b] = fma(-0.5, Fbu, bu[b]);
+            bv[a] = fma(-0.5, Fav, bv[a]); bv[b] = fma(-0.5, Fbv, bv[b]);
+            be[a] = fma(-0.5, Fae, be[a]); be[b] = fma(-0.5, Fbe, be[b]);
+        } else {
+            // Branch-free: a boundary facet carries this cell's own values as "neighbour" traces (finite numbers), its flux is
+            // evaluated like any other and discarded.  With `if (nb[f] >= 0)` around the evaluation the compiler sank the six trace
+            // loads of a facet into the branch - a third dependent trip to memory in every wave.  (The wetting-drying variant keeps
+            // the branch, like the fused viscosity above, whose traces stay live for swe_visc_interior: branch-free it needs
+            // 256 VGPRs = 1 wave/SIMD, 248 instead of 185-198 us/step at 1 M cells.)
+            double L, rL;
+            swe_tri_facet_len(nx[f], ny[f], L, rL);
+            swe_tri_facet<NONLIN, LF, WD, WD>(g, p.sigma_lf, nb[f] < 0, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b], H[a], H[b], al[a],
+                                                      al[b], una[f], unb[f], vna[f], vnb[f], ena[f], enb[f], nx[f], ny[f], L, rL, bu[a], bu[b],
+                                                      bv[a], bv[b], be[a], be[b]);
         }
-        if (nb[f] < 0) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }   // see swe_boundary_epilogue / BINL
-        bu[a] = fma(-0.5, Fau, bu[a]); bu[b] = fma(-0.5, Fbu, bu[b]);
-        bv[a] = fma(-0.5, Fav, bv[a]); bv[b] = fma(-0.5, Fbv, bv[b]);
-        be[a] = fma(-0.5, Fae, be[a]); be[b] = fma(-0.5, Fbe, be[b]);
     }
-
     // optional cell-local terms AFTER the facet loop: the 18 neighbour traces are dead by now, which keeps the SRC variants
     // at 146 (162 with wetting-drying) VGPRs = 3 waves/SIMD instead of 188 (194) = 2
     if (SRC) swe_source_terms<true>(p, k, S, twoA, u, v, H, gxs, gys, bu, bv, be);
     if (VISC) swe_visc_interior(p, k, S8, gu, gv, nb, vid, u, v, una, unb, vna, vnb, px, py, nx, ny, Lf, rLf, twoA, H, bu, bv);
-
-    // ---- mass inverse (M^-1 b)_i = 3/A (4 b_i - sum b), times dt, and the Shu-Osher combine
-    const double s = 6.0*p.dt*p.beta*swe_rcp(twoA);
-    const double su = bu[0] + bu[1] + bu[2], sv = bv[0] + bv[1] + bv[2], se = be[0] + be[1] + be[2];
-    double ou[3], ov[3], oe[3];
+    if constexpr (VISC) {
+        const double s = 6.0*p.dt*p.beta*swe_rcp(twoA);
+        const double su = bu[0] + bu[1] + bu[2], sv = bv[0] + bv[1] + bv[2], se = be[0] + be[1] + be[2];
 #pragma unroll
-    for (int i = 0; i < 3; i++) {
-        ou[i] = fma(s, fma(4.0, bu[i], -su), wu[i]);
-        ov[i] = fma(s, fma(4.0, bv[i], -sv), wv[i]);
-        oe[i] = fma(s, fma(4.0, be[i], -se), we[i]);          // eta, or zeta = D - h with wetting-drying
-    }
-    // boundary facets were skipped above; their correction is added to the finished outputs (see swe_boundary_epilogue)
-    if (BINL && bmarkers != 0) {
-        // Boundary facets from the values this lane still holds (no second trip to memory: on a small grid the dependent
-        // reloads of swe_boundary_epilogue made the boundary waves the last ones to finish).  Every lane works on ITS
-        // boundary facet - the wave runs the boundary code once (twice where a corner cell is among its lanes), not once per
-        // facet slot - in ascending facet order and with the arithmetic of swe_boundary_epilogue: the same bits.
-#pragma clang fp contract(off)
-        // 2A exactly as swe_boundary_epilogue forms it, from the facet normals that are still live: x1 - x0 = -ny[0],
-        // y2 - y0 = -nx[2], y1 - y0 = nx[0], x2 - x0 = ny[2] (negation is exact)
-        const double sfac = 6.0*p.dt*p.beta*swe_rcp(fma(-ny[0], -nx[2], -(nx[0]*ny[2])));
-        int rem = ((bmarkers & 0xff) ? 1 : 0) | ((bmarkers & 0xff00) ? 2 : 0) | ((bmarkers & 0xff0000) ? 4 : 0);
-        int kind_next = bkind1;                     // first pass: prefetched; a second pass (corner cell) reads the table
-#define SWE_SEL3(x, i) ((i) == 0 ? (x)[0] : ((i) == 1 ? (x)[1] : (x)[2]))
-#pragma unroll 1
-        while (rem) {
-            const int f = (rem & 1) ? 0 : ((rem & 2) ? 1 : 2);
-            rem &= rem - 1;
-            const int a = f, b = (f == 2) ? 0 : f + 1;
-            const double nxs = SWE_SEL3(nx, f), nys = SWE_SEL3(ny, f);
-            double L, rL;
-            swe_sqrt_rsqrt(swe_dot2(nxs, nxs, nys, nys), L, rL);
-            double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
-            // (nodal depth: h + eta re-formed here for the plain nonlinear case instead of keeping H[] live - the same sum)
-            const double Ha_ = (WD || !NONLIN) ? SWE_SEL3(H, a) : SWE_SEL3(h, a) + SWE_SEL3(e, a);
-            const double Hb_ = (WD || !NONLIN) ? SWE_SEL3(H, b) : SWE_SEL3(h, b) + SWE_SEL3(e, b);
-            swe_boundary_facet<NONLIN, LF, WD>(p, (bmarkers >> (8*f)) & 0xff, k, a, b, SWE_SEL3(u, a), SWE_SEL3(u, b), SWE_SEL3(v, a),
-                                               SWE_SEL3(v, b), SWE_SEL3(e, a), SWE_SEL3(e, b), SWE_SEL3(h, a), SWE_SEL3(h, b),
-                                               Ha_, Hb_, SWE_SEL3(al, a), SWE_SEL3(al, b), nxs, nys, L, rL,
-                                               Fau, Fbu, Fav, Fbv, Fae, Fbe, kind_next);
-            kind_next = -1;
-            const double dau = -0.5*Fau, dbu = -0.5*Fbu, dav = -0.5*Fav, dbv = -0.5*Fbv, dae = -0.5*Fae, dbe = -0.5*Fbe;
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const double wa = (i == a) ? 3.0 : -1.0, wb = (i == b) ? 3.0 : -1.0;
-                ou[i] = fma(sfac, fma(wa, dau, wb*dbu), ou[i]);      // as in swe_boundary_epilogue, bit for bit
-                ov[i] = fma(sfac, fma(wa, dav, wb*dbv), ov[i]);
-                oe[i] = fma(sfac, fma(wa, dae, wb*dbe), oe[i]);
-            }
+        for (int i = 0; i < 3; i++) {
+            ou[i] = fma(s, fma(4.0, bu[i], -su), wu[i]);
+            ov[i] = fma(s, fma(4.0, bv[i], -sv), wv[i]);
+            oe[i] = fma(s, fma(4.0, be[i], -se), we[i]);
         }
-#undef SWE_SEL3
+    } else {
+        swe_tri_finish<NONLIN, LF, WD, true>(p, k, p.beta, twoA, u, v, e, h, H, al, nx, ny, BINL ? bmarkers : 0, bkind1, bu, bv, be,
+                                             wu, wv, we, BINL && wd_fin, ou, ov, oe);
     }
-    if (!BINL && (nb[0] | nb[1] | nb[2]) < 0) swe_boundary_epilogue<NONLIN, LF, WD>(p, k, nb[0], nb[1], nb[2], ou, ov, oe);
+    // (the limiter comes after ALL boundary fluxes: with the inline pass that is inside swe_tri_finish, hence `BINL && wd_fin` above;
+    //  the variant that reloads the boundary facets' nodes runs its epilogue first)
+    if (!BINL) {
+        if ((nb[0] | nb[1] | nb[2]) < 0) swe_boundary_epilogue<NONLIN, LF, WD>(p, k, nb[0], nb[1], nb[2], ou, ov, oe);
+        if (wd_fin) swe_wd_finish<3>(g, p.beta*p.dt, h, al, ou, ov, oe, !p.wd_skip_relax);
+    }
     const swe_rsrc_t gou = swe_rsrc(p.uout), gov = swe_rsrc(p.uout + 3*S), goe = swe_rsrc(p.uout + 6*S);
 #ifdef SWE_WAVE_TIMING
     if (ou[0] == 1.2345e300) return;          // the arithmetic has to be finished before the time stamp
     SWE_WT(3);
 #endif
-    // zeta = D - h -> limited depth D (stored); dry-ground relaxation.  (Not for the parity hook swe2d_tendency, a0 = a1 = 0: it
-    // returns the raw tendencies of (u, v, zeta).)
-    if (WD && !(p.a0 == 0.0 && p.a1 == 0.0)) swe_wd_finish<3>(g, p.beta*p.dt, h, al, ou, ov, oe, !p.wd_skip_relax);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         swe_st(gou, k8, i*S8, ou[i]);
