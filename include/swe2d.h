@@ -677,6 +677,45 @@ int  swe2d_stats_read(swe2d_handle *h, int32_t stats_id, double *out, int64_t *n
 int  swe2d_stats_reset(swe2d_handle *h, int32_t stats_id);
 int  swe2d_stats_destroy(swe2d_handle *h, int32_t stats_id);
 
+/* ---- Lagrangian particle tracking: drifters advected in the velocity field of the state, one explicit-midpoint move per call.
+ * A particle set holds N particles: position (double x, y), cell (the handle's own numbering), status, the marker it left through,
+ * a wall-hit counter, and `capacity` rows [N][2] of recorded positions.  Triangles only (SWE2D_ERR_UNSUPPORTED on quadrilaterals).
+ * swe2d_particles_advance is ONE launch on the handle's stream, no synchronisation: every ACTIVE particle makes, in the velocity of
+ * buffer A frozen over the move and left to right without contraction (only + - * / and comparisons: a host replay has its bits),
+ *     u1 = U(x, k);   (xm, km) = probe(x, k, (0.5*dt_move)*u1);   u2 = U(xm, km);   (x', k') = move(x, k, dt_move*u2)
+ * U(x, k): with the cell's vertices p0, p1, p2:  a = p1 - p0, b = p2 - p0, det = a.x*b.y - b.x*a.y, d = x - p0,
+ *     l1 = (d.x*b.y - b.x*d.y)/det,  l2 = (a.x*d.y - d.x*a.y)/det,  l0 = (1 - l1) - l2,   U = (l0*u0 + l1*u1) + l2*u2 per component.
+ *     The coordinate that vanishes on facet f (which joins the local vertices f, f + 1) is m_f = l_((f + 2) % 3).
+ * move(x, k, d): the straight walk along x -> y = x + d.  In the current cell form m_f(x), m_f(y).  The candidates are the facets
+ *     with m_f(y) < 0, the facet just entered through excepted; without a candidate the particle arrives at (y, cell).  Else the
+ *     candidate of the smallest s_f = m_f(x)/(m_f(x) - m_f(y)) is crossed (ties: the lowest f): an interior facet continues in the
+ *     neighbour; a boundary facet whose marker is open sets EXITED, stores the marker and freezes the particle at x + s*d; any other
+ *     boundary is a wall: the particle arrives at x + (s*(1 - 2^-10))*d in that cell, stays ACTIVE, its wall-hit counter goes up by one.
+ *     A walk that has not arrived within SWE2D_PARTICLE_MAX_HOPS cells makes the particle LOST at its position before the advance (a
+ *     bound on the loop, not a tolerance).  probe() is the same walk without consequences: an open boundary or a wall only ends it,
+ *     at the crossing point or the shortened point; a probe that does not arrive makes the particle LOST as well.
+ * EXITED and LOST particles are never touched again.  Every call inside a stream capture returns SWE2D_ERR_UNSUPPORTED.  No reference
+ * counterpart (the reference has no 2D particle tracker). */
+#define SWE2D_PARTICLE_ACTIVE 0
+#define SWE2D_PARTICLE_EXITED 1
+#define SWE2D_PARTICLE_LOST 2
+#define SWE2D_PARTICLE_MAX_HOPS 64
+/* xy [n][2], cells [n]: every cell in range and every position inside its cell (all three coordinates >= -1e-12), else
+ * SWE2D_ERR_INVALID_ARGUMENT; capacity >= 0 rows.  An allocation failure (SWE2D_ERR_HIP, the message names the bytes asked for)
+ * leaves the handle as it was. */
+int  swe2d_particles_create(swe2d_handle *h, int32_t n_particles, const double *xy, const int32_t *cells, int32_t capacity,
+                            int32_t *particles_id);
+/* one move of every ACTIVE particle (asynchronous); open_markers [n_open], n_open <= SWE2D_MAX_MARKERS, each in 1..SWE2D_MAX_MARKERS-1 */
+int  swe2d_particles_advance(swe2d_handle *h, int32_t particles_id, double dt_move, int32_t n_open, const int32_t *open_markers);
+/* the current positions as one more row (asynchronous); SWE2D_ERR_INVALID_ARGUMENT and nothing written when the set holds `capacity` rows */
+int  swe2d_particles_record(swe2d_handle *h, int32_t particles_id);
+/* synchronises; xy [n][2], cells, status, exit_markers (0: none), wall_hits [n]; any of them may be NULL */
+int  swe2d_particles_read(swe2d_handle *h, int32_t particles_id, double *xy, int32_t *cells, int32_t *status, int32_t *exit_markers,
+                          int32_t *wall_hits);
+/* the rows recorded since the last read -> out [rows][n][2] (room for `capacity` rows), then the row buffer is empty */
+int  swe2d_particles_read_rows(swe2d_handle *h, int32_t particles_id, double *out, int32_t *n_rows);
+int  swe2d_particles_destroy(swe2d_handle *h, int32_t particles_id);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,9 @@ ATM_WIND, ATM_PRESSURE = 1, 2         # include/swe2d.h SWE2D_ATM_*: the quantit
 ATM_METHODS = {'LargeYeager2009': 0, 'LargePond1981': 1, 'SmithBanke1975': 2}     # include/swe2d.h SWE2D_ATM_<formulation>
 ATM_RHO_AIR = 1.22                    # include/swe2d.h SWE2D_ATM_RHO_AIR
 STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
-PROBE_UV, PROBE_ELEV = -1, -2   # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
+PARTICLE_ACTIVE, PARTICLE_EXITED, PARTICLE_LOST = 0, 1, 2   # include/swe2d.h SWE2D_PARTICLE_*: status of a tracked particle
+PARTICLE_MAX_HOPS = 64                # include/swe2d.h SWE2D_PARTICLE_MAX_HOPS: cells one walk may visit
+PROBE_UV, PROBE_ELEV = -1, -2  # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
 # The library itself never reads the environment (include/swe2d.h, swe2d_set_option).  As a convenience of THIS binding the variables
@@ -231,6 +233,12 @@ SYMBOLS = {
     'swe2d_stats_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64)]),
     'swe2d_stats_reset': (ctypes.c_int, [_H, ctypes.c_int32]),
     'swe2d_stats_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_particles_create': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip, ctypes.c_int32, _ip]),
+    'swe2d_particles_advance': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _ip]),
+    'swe2d_particles_record': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_particles_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip, _ip, _ip, _ip]),
+    'swe2d_particles_read_rows': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip]),
+    'swe2d_particles_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
 }
 
 _lib = None

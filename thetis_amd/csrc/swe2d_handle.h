@@ -297,6 +297,15 @@ struct Handle {
         long long n_samples = 0;                        // appends since create / reset
     };
     std::vector<Stats> stats;
+    // Lagrangian particles (swe2d_particles.hip): slot = particle set id; a destroyed set leaves an empty slot
+    struct Particles {
+        bool live = false;
+        int n = 0, capacity = 0, rows = 0;
+        double *pos = nullptr;                          // [n][2] x, y
+        int *ist = nullptr;                             // cell [n] | status [n] | exit marker [n] | wall hits [n]
+        double *out = nullptr;                          // [capacity][n][2] recorded positions
+    };
+    std::vector<Particles> particles;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -448,6 +457,8 @@ int atm_launch(Handle *h, double t);                    // one launch: wind stre
 int atm_check_advance(Handle *h, int n_steps, bool forward_euler);   // SWE2D_ERR_INVALID_ARGUMENT where a stage time of the advance leaves the record
 // ---- running field statistics (swe2d_stats.hip): frees every statistics set of the handle (swe2d_destroy)
 void stats_free_all(Handle *h);
+// ---- Lagrangian particles (swe2d_particles.hip): frees every particle set of the handle (swe2d_destroy)
+void particles_free_all(Handle *h);
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -1,0 +1,330 @@
+// swe2d_particles.hip - Lagrangian particle tracking: the swe2d_particles_* entry points and the advection kernel.
+//
+// A particle set holds, per particle, its position [n][2], its cell, status, exit marker and wall-hit counter (four int planes [n]),
+// and `capacity` rows [n][2] of recorded positions.  swe_particle_kernel - one lane per particle - makes one explicit-midpoint move in
+// the velocity planes of buffer A, frozen over the move:
+//
+//     u1 = U(x, k);   (xm, km) = probe(x, k, (0.5*dt_move)*u1);   u2 = U(xm, km);   (x', k') = move(x, k, dt_move*u2)
+//
+// with U the P1 interpolation of the cell's nodal velocities and move() the straight walk from cell to cell through the packed
+// neighbour codes (include/swe2d.h has the formulas, thetis_amd/particles.py restates them in numpy).  Everything is evaluated left
+// to right without contraction and uses + - * / and comparisons only, so a host replay has the bits of the device.  The walk is a
+// divergent gather by nature: per cell visited a lane reads 3 vertex ids, 6 vertex coordinates and 1 neighbour code (64 B), per
+// velocity 6 nodal values and the cell's geometry (108 B); per advance 16 B of position and 8 B of cell / status are read, 16 + 4 B
+// written (more on an exit or a wall hit).  No LDS, no atomics, every particle has exactly one writer.  The plane pointers are taken
+// from the handle when the launch is enqueued, so an advance after a launch that swapped the state buffers (swe_fuse123_kernel)
+// sees the step result, as a probe row does.
+#include "swe2d_handle.h"
+
+#ifndef SWE_RANGE_CHECK
+__device__ __forceinline__ void swe_sti(swe_rsrc_t r, unsigned voff, unsigned soff, int x)
+{
+    __builtin_amdgcn_raw_buffer_store_b32((unsigned)x, r, voff, soff, 0);
+}
+#else
+__device__ __forceinline__ void swe_sti_chk(swe_rsrc_t r, unsigned voff, unsigned soff, int x, int line)
+{
+    if (!swe_chk(r.base + voff + soff, 4, line)) return;
+    __builtin_amdgcn_raw_buffer_store_b32((unsigned)x, r.r, voff, soff, 0);
+}
+#define swe_sti(r, v, s, x) swe_sti_chk(r, v, s, x, __LINE__)
+#endif
+
+struct SweParticleArgs {
+    const double *state;                        // buffer A: u planes | v planes | elevation planes, [9][stride]
+    const int *cv, *nbr;                        // [3][stride] cell vertices, packed neighbour codes
+    const double *vx, *vy;                      // vertex coordinates
+    double *pos;                                // [n][2]
+    int *ist;                                   // cell [n] | status [n] | exit marker [n] | wall hits [n]
+    size_t stride;
+    double dt_move;
+    int n;
+    unsigned open_mask;                         // bit m: boundary marker m is open
+};
+
+struct SweParticleCell { double x0, y0, ax, ay, bx, by, det; };
+
+enum { SWE_WALK_ARRIVED = 0, SWE_WALK_EXIT = 1, SWE_WALK_WALL = 2, SWE_WALK_LOST = 3 };
+
+__device__ __forceinline__ SweParticleCell swe_particle_cell(const SweParticleArgs &a, int k)
+{
+#pragma clang fp contract(off)
+    const unsigned k4 = (unsigned)k*4u, S4 = (unsigned)a.stride*4u;
+    const swe_rsrc_t rc = swe_rsrc(a.cv), rx = swe_rsrc(a.vx), ry = swe_rsrc(a.vy);
+    const unsigned v0 = (unsigned)swe_ldi(rc, k4, 0u)*8u, v1 = (unsigned)swe_ldi(rc, k4, S4)*8u, v2 = (unsigned)swe_ldi(rc, k4, 2u*S4)*8u;
+    SweParticleCell c;
+    c.x0 = swe_ld(rx, v0, 0u);
+    c.y0 = swe_ld(ry, v0, 0u);
+    c.ax = swe_ld(rx, v1, 0u) - c.x0;
+    c.ay = swe_ld(ry, v1, 0u) - c.y0;
+    c.bx = swe_ld(rx, v2, 0u) - c.x0;
+    c.by = swe_ld(ry, v2, 0u) - c.y0;
+    c.det = c.ax*c.by - c.bx*c.ay;
+    return c;
+}
+
+// m[f]: the barycentric coordinate that vanishes on facet f (the one of the local vertex (f + 2) % 3)
+__device__ __forceinline__ void swe_particle_bary(const SweParticleCell &c, double px, double py, double m[3])
+{
+#pragma clang fp contract(off)
+    const double dx = px - c.x0, dy = py - c.y0;
+    const double l1 = (dx*c.by - c.bx*dy)/c.det;
+    const double l2 = (c.ax*dy - dx*c.ay)/c.det;
+    const double l0 = (1.0 - l1) - l2;
+    m[0] = l2; m[1] = l0; m[2] = l1;
+}
+
+__device__ __forceinline__ void swe_particle_velocity(const SweParticleArgs &a, int k, double px, double py, double &u, double &v)
+{
+#pragma clang fp contract(off)
+    const SweParticleCell c = swe_particle_cell(a, k);
+    double m[3];
+    swe_particle_bary(c, px, py, m);
+    const unsigned k8 = (unsigned)k*8u, S8 = (unsigned)a.stride*8u;
+    const swe_rsrc_t gu = swe_rsrc(a.state), gv = swe_rsrc(a.state + 3*a.stride);
+    const double u0 = swe_ld(gu, k8, 0u), u1 = swe_ld(gu, k8, S8), u2 = swe_ld(gu, k8, 2u*S8);
+    const double v0 = swe_ld(gv, k8, 0u), v1 = swe_ld(gv, k8, S8), v2 = swe_ld(gv, k8, 2u*S8);
+    u = (m[1]*u0 + m[2]*u1) + m[0]*u2;
+    v = (m[1]*v0 + m[2]*v1) + m[0]*v2;
+}
+
+// the straight walk along (x, y) -> (x + dx, y + dy) from cell k: where it ends (ox, oy, ok), how, and through which marker
+__device__ __forceinline__ int swe_particle_walk(const SweParticleArgs &a, double x, double y, int k, double dx, double dy,
+                                                 double &ox, double &oy, int &ok, int &marker)
+{
+#pragma clang fp contract(off)
+    const double tx = x + dx, ty = y + dy;
+    const unsigned S4 = (unsigned)a.stride*4u;
+    const swe_rsrc_t rn = swe_rsrc(a.nbr);
+    int from = -1;
+    for (int hop = 0; hop < SWE2D_PARTICLE_MAX_HOPS; hop++) {          // bounded: no lane loops forever
+        const SweParticleCell c = swe_particle_cell(a, k);
+        double mx[3], my[3];
+        swe_particle_bary(c, x, y, mx);
+        swe_particle_bary(c, tx, ty, my);
+        int best = -1;
+        double sb = 0.0;
+#pragma unroll
+        for (int f = 0; f < 3; f++) {
+            if (f != from && my[f] < 0.0) {
+                const double s = mx[f]/(mx[f] - my[f]);
+                if (best < 0 || s < sb) { best = f; sb = s; }
+            }
+        }
+        if (best < 0) { ox = tx; oy = ty; ok = k; return SWE_WALK_ARRIVED; }
+        const int code = swe_ldi(rn, (unsigned)k*4u + (unsigned)best*S4, 0u);
+        if (code >= 0) { from = code & 3; k = code >> 2; continue; }
+        marker = -code;
+        ok = k;
+        if (marker < SWE2D_MAX_MARKERS && ((a.open_mask >> marker) & 1u)) {
+            ox = x + sb*dx; oy = y + sb*dy;
+            return SWE_WALK_EXIT;
+        }
+        const double f = sb*(1.0 - 0x1p-10);
+        ox = x + f*dx; oy = y + f*dy;
+        return SWE_WALK_WALL;
+    }
+    return SWE_WALK_LOST;
+}
+
+__global__ void __launch_bounds__(256) swe_particle_kernel(SweParticleArgs a)
+{
+#pragma clang fp contract(off)
+    const int p = blockIdx.x*blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    const swe_rsrc_t ri = swe_rsrc(a.ist), rp = swe_rsrc(a.pos);
+    const unsigned p4 = (unsigned)p*4u, p16 = (unsigned)p*16u, N4 = (unsigned)a.n*4u;
+    if (swe_ldi(ri, p4, N4) != SWE2D_PARTICLE_ACTIVE) return;
+    const int k = swe_ldi(ri, p4, 0u);
+    const double x = swe_ld(rp, p16, 0u), y = swe_ld(rp, p16, 8u);
+    double u, v, xm, ym, xn, yn;
+    int km, kn, marker = 0;
+    swe_particle_velocity(a, k, x, y, u, v);
+    const double half = 0.5*a.dt_move;
+    int how = swe_particle_walk(a, x, y, k, half*u, half*v, xm, ym, km, marker);
+    if (how != SWE_WALK_LOST) {
+        swe_particle_velocity(a, km, xm, ym, u, v);
+        how = swe_particle_walk(a, x, y, k, a.dt_move*u, a.dt_move*v, xn, yn, kn, marker);
+    }
+    if (how == SWE_WALK_LOST) {
+        swe_sti(ri, p4, N4, SWE2D_PARTICLE_LOST);
+        return;
+    }
+    swe_st(rp, p16, 0u, xn);
+    swe_st(rp, p16, 8u, yn);
+    swe_sti(ri, p4, 0u, kn);
+    if (how == SWE_WALK_EXIT) {
+        swe_sti(ri, p4, N4, SWE2D_PARTICLE_EXITED);
+        swe_sti(ri, p4, 2u*N4, marker);
+    } else if (how == SWE_WALK_WALL) {
+        swe_sti(ri, p4, 3u*N4, swe_ldi(ri, p4, 3u*N4) + 1);
+    }
+}
+
+namespace {
+
+const int kParticlesMax = 1 << 27;              // 16 B of position per particle behind a 32-bit offset
+
+int particles_check(Handle *h, int id, Handle::Particles **out)
+{
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "particle calls are not allowed inside a stream capture");
+    if (id < 0 || id >= (int)h->particles.size() || !h->particles[id].live)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "no such particle set");
+    *out = &h->particles[id];
+    return SWE2D_OK;
+}
+
+void particles_release(Handle::Particles &s)
+{
+    if (s.pos) (void)hipFree(s.pos);
+    if (s.ist) (void)hipFree(s.ist);
+    if (s.out) (void)hipFree(s.out);
+    s = Handle::Particles();
+}
+
+}  // namespace
+
+void swe2d_impl::particles_free_all(Handle *h)
+{
+    for (auto &s : h->particles) particles_release(s);
+    h->particles.clear();
+}
+
+int swe2d_particles_create(swe2d_handle *hh, int32_t n, const double *xy, const int32_t *cells, int32_t capacity, int32_t *particles_id)
+{
+    Handle *h = H(hh);
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "particle calls are not allowed inside a stream capture");
+    if (h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_particles_create: particles are tracked on triangles only");
+    if (n <= 0 || n > kParticlesMax || !xy || !cells || capacity < 0 || !particles_id)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_create: bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    {   // every cell in range, every position inside its cell: the formulas of the kernel on the host's copy of the vertices
+        std::vector<double> vx((size_t)h->n_vertices), vy((size_t)h->n_vertices);
+        HIP_TRY(h, hipMemcpy(vx.data(), h->vx, vx.size()*sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(vy.data(), h->vy, vy.size()*sizeof(double), hipMemcpyDeviceToHost));
+        for (int p = 0; p < n; p++) {
+            const int k = cells[p];
+            if (k < 0 || k >= h->n_cells) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_create: cell out of range");
+            const int *v = &h->host_cells[(size_t)3*k];
+            const double x0 = vx[v[0]], y0 = vy[v[0]], ax = vx[v[1]] - x0, ay = vy[v[1]] - y0, bx = vx[v[2]] - x0, by = vy[v[2]] - y0;
+            const double det = ax*by - bx*ay, dx = xy[2*(size_t)p] - x0, dy = xy[2*(size_t)p + 1] - y0;
+            const double l1 = (dx*by - bx*dy)/det, l2 = (ax*dy - dx*ay)/det, l0 = (1.0 - l1) - l2;
+            if (!(l0 >= -1e-12 && l1 >= -1e-12 && l2 >= -1e-12))
+                return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_create: particle " + std::to_string(p) + " is not inside its cell");
+        }
+    }
+    Handle::Particles s;
+    s.n = n; s.capacity = capacity;
+    const size_t pos_bytes = (size_t)n*2*sizeof(double), ist_bytes = (size_t)n*4*sizeof(int),
+                 out_bytes = (size_t)std::max(capacity, 1)*pos_bytes;
+    hipError_t e = hipMalloc(&s.pos, pos_bytes);
+    if (e == hipSuccess) e = hipMalloc(&s.ist, ist_bytes);
+    if (e == hipSuccess) e = hipMalloc(&s.out, out_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        particles_release(s);
+        return fail(h, SWE2D_ERR_HIP, "swe2d_particles_create: " + std::to_string(pos_bytes + ist_bytes + out_bytes)
+                    + " bytes of particle state and rows: " + hipGetErrorString(e));
+    }
+    e = hipMemcpyAsync(s.pos, xy, pos_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.ist, 0, ist_bytes, h->stream);       // ACTIVE, no marker, no hits
+    if (e == hipSuccess) e = hipMemcpyAsync(s.ist, cells, (size_t)n*sizeof(int), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);                      // the host arrays may be reused by the caller
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        particles_release(s);
+        return fail(h, SWE2D_ERR_HIP, std::string("swe2d_particles_create: ") + hipGetErrorString(e));
+    }
+    s.live = true;
+    int id = 0;
+    while (id < (int)h->particles.size() && h->particles[id].live) id++;
+    if (id == (int)h->particles.size()) h->particles.push_back(s); else h->particles[id] = s;
+    *particles_id = id;
+    return SWE2D_OK;
+}
+
+int swe2d_particles_advance(swe2d_handle *hh, int32_t id, double dt_move, int32_t n_open, const int32_t *open_markers)
+{
+    Handle *h = H(hh);
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (n_open < 0 || n_open > SWE2D_MAX_MARKERS || (n_open > 0 && !open_markers) || !std::isfinite(dt_move))
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance: bad argument");
+    unsigned mask = 0u;
+    for (int j = 0; j < n_open; j++) {
+        if (open_markers[j] < 1 || open_markers[j] >= SWE2D_MAX_MARKERS)
+            return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance: open markers must be in 1..SWE2D_MAX_MARKERS-1");
+        mask |= 1u << open_markers[j];
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    SweParticleArgs a{};
+    a.state = h->state[0];
+    a.cv = h->cv; a.nbr = h->nbr; a.vx = h->vx; a.vy = h->vy;
+    a.pos = s->pos; a.ist = s->ist;
+    a.stride = h->stride;
+    a.dt_move = dt_move;
+    a.n = s->n;
+    a.open_mask = mask;
+    SWE_CHK_SYNC(h->stream);
+    hipLaunchKernelGGL(swe_particle_kernel, dim3((unsigned)grid_for(s->n)), dim3(256), 0, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return SWE2D_OK;
+}
+
+int swe2d_particles_record(swe2d_handle *hh, int32_t id)
+{
+    Handle *h = H(hh);
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (s->rows >= s->capacity) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_record: the row buffer is full (read it first)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t row = (size_t)s->n*2;
+    HIP_TRY(h, hipMemcpyAsync(s->out + (size_t)s->rows*row, s->pos, row*sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    s->rows++;
+    return SWE2D_OK;
+}
+
+int swe2d_particles_read(swe2d_handle *hh, int32_t id, double *xy, int32_t *cells, int32_t *status, int32_t *exit_markers, int32_t *wall_hits)
+{
+    Handle *h = H(hh);
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)s->n;
+    if (xy) HIP_TRY(h, hipMemcpyAsync(xy, s->pos, 2*n*sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int32_t *dst[4] = {cells, status, exit_markers, wall_hits};
+    for (int j = 0; j < 4; j++)
+        if (dst[j]) HIP_TRY(h, hipMemcpyAsync(dst[j], s->ist + (size_t)j*n, n*sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = capture_parity_check(h)) return rc;
+    return flow_check(h);
+}
+
+int swe2d_particles_read_rows(swe2d_handle *hh, int32_t id, double *out, int32_t *n_rows)
+{
+    Handle *h = H(hh);
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (!out || !n_rows) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (s->rows > 0)
+        HIP_TRY(h, hipMemcpyAsync(out, s->out, (size_t)s->rows*s->n*2*sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *n_rows = s->rows;
+    s->rows = 0;
+    if (int rc = capture_parity_check(h)) return rc;
+    return flow_check(h);
+}
+
+int swe2d_particles_destroy(swe2d_handle *hh, int32_t id)
+{
+    Handle *h = H(hh);
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                           // moves may still be in flight
+    particles_release(*s);
+    return SWE2D_OK;
+}

@@ -807,6 +807,56 @@ class Swe2dDevice(object):
     def stats_destroy(self, sid):
         self._ck(self.lib.swe2d_stats_destroy(self.h, int(sid)))
 
+    # -- Lagrangian particles: csrc/swe2d_particles.hip
+    def particles_create(self, xy, cells, capacity=0):
+        """A particle set of the positions ``xy`` (N, 2) in the ``cells`` (N,) that contain them (caller numbering;
+        thetis_amd/pointeval.py locates them) with room for ``capacity`` recorded rows.  Returns its id."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+        if len(cells) != len(xy):
+            raise ValueError('one cell per particle')
+        if len(cells) and (cells.min() < 0 or cells.max() >= self.n_cells):
+            raise _lib.Swe2dError(_lib.ERR_INVALID_ARGUMENT, 'particles_create: cell out of range')
+        dev = np.ascontiguousarray((cells if self.perm is None else self.inv_perm[cells]).astype(np.int32))
+        pid = ctypes.c_int32()
+        self._ck(self.lib.swe2d_particles_create(self.h, len(dev), _ptr(xy), _iptr(dev), int(capacity), ctypes.byref(pid)))
+        self.__dict__.setdefault('_particles_shape', {})[pid.value] = (len(dev), int(capacity))
+        return pid.value
+
+    def particles_advance(self, pid, dt_move, open_markers=()):
+        """one explicit-midpoint move of every active particle in the current velocity, enqueued (no synchronisation);
+        ``open_markers``: the boundary markers a particle leaves through (every other boundary is a wall)"""
+        slots = np.ascontiguousarray([self._slot(m) for m in open_markers], dtype=np.int32)
+        self._ck(self.lib.swe2d_particles_advance(self.h, int(pid), float(dt_move), len(slots), _iptr(slots) if len(slots) else None))
+
+    def particles_record(self, pid):
+        """the current positions as one more row of the set, enqueued; raises when the set already holds ``capacity`` rows"""
+        self._ck(self.lib.swe2d_particles_record(self.h, int(pid)))
+
+    def particles_read(self, pid):
+        """(positions (N, 2), cells (N,) in the caller's numbering, status, exit markers (0: none), wall hits); synchronises"""
+        n, _ = self._particles_shape[int(pid)]
+        xy = np.empty((n, 2))
+        cells, status, markers, hits = (np.empty(n, dtype=np.int32) for _ in range(4))
+        self._ck(self.lib.swe2d_particles_read(self.h, int(pid), _ptr(xy), _iptr(cells), _iptr(status), _iptr(markers), _iptr(hits)))
+        if self.perm is not None:
+            cells = np.asarray(self.perm)[cells].astype(np.int32)
+        back = np.zeros(_lib.MAX_MARKERS, dtype=np.int64)
+        for m, sl in self._marker_slot.items():
+            back[sl] = m
+        return xy, cells, status, back[markers].astype(np.int32), hits
+
+    def particles_read_rows(self, pid):
+        """(rows, N, 2): the rows recorded since the last read; synchronises and empties the row buffer"""
+        n, capacity = self._particles_shape[int(pid)]
+        out = np.empty((max(capacity, 1), n, 2))
+        k = ctypes.c_int32()
+        self._ck(self.lib.swe2d_particles_read_rows(self.h, int(pid), _ptr(out), ctypes.byref(k)))
+        return out[:k.value].copy()
+
+    def particles_destroy(self, pid):
+        self._ck(self.lib.swe2d_particles_destroy(self.h, int(pid)))
+
     # -- tracers + limiter
     def _nodal_in(self, a):
         a = np.asarray(a, dtype=np.float64).reshape(self.n_cells, self.npc)

@@ -27,7 +27,7 @@ def exercise():
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
         for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'atm', 'stats',
-                        'stats+wetting-drying'):
+                        'stats+wetting-drying', 'particles', 'particles+wetting-drying'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
             bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') or variant == 'dfarm' else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
@@ -42,7 +42,7 @@ def exercise():
             if variant == 'viscosity':
                 dev.set_viscosity(20.0 + 5.0*np.arange(mesh.num_vertices)/mesh.num_vertices, use_grad_div_viscosity_term=True)
                 dev.set_bc(markers[0], {'un': 0.1})
-            if variant in ('wetting-drying', 'stats+wetting-drying'):
+            if variant in ('wetting-drying', 'stats+wetting-drying', 'particles+wetting-drying'):
                 dev.set_wetting_and_drying(0.5)
                 dev.set_scalar(_lib.SCALAR_MANNING_DRAG, 0.02)
             if variant.startswith('farms'):
@@ -159,6 +159,39 @@ def exercise():
                     assert (acc[0] <= acc[1]).all() and (acc[2] >= 0).all()
                 dev.stats_destroy(sets[5])
                 n_launch += 12
+            if variant.startswith('particles'):
+                # Lagrangian particles: swe_particle_kernel reads the cell vertices, the vertex coordinates, the neighbour codes and the
+                # velocity planes of every cell a walk visits and reads / writes the position and the four int planes of its set
+                # through the checked accesses (the rows are copied by the runtime).  Short moves, moves across many cells that end at
+                # walls and open boundaries, and moves that reach the hop cap; one particle, a partial and several workgroups.
+                # Quadrilaterals: the set is refused.
+                rng = np.random.default_rng(9)
+                if k != 3:
+                    try:
+                        dev.particles_create(cxy[:1].mean(axis=1), [0])
+                        raise AssertionError('a particle set on quadrilaterals')
+                    except _lib.Swe2dError as e:
+                        assert e.code == _lib.ERR_UNSUPPORTED
+                else:
+                    span = np.ptp(cxy.reshape(-1, 2), axis=0).max()
+                    sets = []
+                    for n_p in (1, 200, 700):
+                        pc = rng.integers(0, mesh.num_cells, size=n_p)
+                        w = rng.uniform(0.05, 1.0, size=(n_p, 3))
+                        w /= w.sum(axis=1, keepdims=True)
+                        sets.append(dev.particles_create((w[:, :, None]*cxy[pc]).sum(axis=1), pc, capacity=4))
+                    for dt_move in (0.01*span, 2.0*span, 200.0*span):       # |u| ~ 0.05: a fraction of a cell ... past the hop cap
+                        dev.advance(1)
+                        for pid in sets:
+                            dev.particles_advance(pid, dt_move, markers[:1])
+                            dev.particles_record(pid)
+                    for pid in sets:
+                        xy_p, cells_p, status_p, _, _ = dev.particles_read(pid)
+                        assert np.isfinite(xy_p).all() and cells_p.min() >= 0 and cells_p.max() < mesh.num_cells, (name, variant)
+                        assert dev.particles_read_rows(pid).shape[0] == 3
+                    assert (dev.particles_read(sets[2])[2] != 0).any(), (name, variant)
+                    dev.particles_destroy(sets[1])
+                    n_launch += 9
             if variant == 'tracers':
                 tid = dev.add_tracer()
                 dev.tracer_set_state(tid, 1.0 + 0.1*np.random.default_rng(0).normal(size=(mesh.num_cells, k)))
