@@ -716,6 +716,62 @@ int  swe2d_particles_read(swe2d_handle *h, int32_t particles_id, double *xy, int
 int  swe2d_particles_read_rows(swe2d_handle *h, int32_t particles_id, double *out, int32_t *n_rows);
 int  swe2d_particles_destroy(swe2d_handle *h, int32_t particles_id);
 
+/* ---- Reacting tracers: a tracer's source as an expression of tracer fields, evaluated in front of every stage of that tracer.
+ * The source term of the reference is inner(source, test)*dx with the live Functions (tracer_eq_2d.py:281-298).  Here a tracer
+ * may carry a PROGRAM: postfix code on a stack of doubles, one int32 word per instruction, op | arg << 8.  Every launch of a stage of
+ * that tracer (swe2d_tracer_solve_stage[_cells], swe2d_tracer_forward_euler, swe2d_tracer_tendency, swe2d_advance_coupled) is preceded by
+ * ONE launch over the same cell range that writes the tracer's nodal source planes (what swe2d_tracer_set_source uploads otherwise);
+ * the stage kernels are the ones of a sourced tracer.  Per cell, left to right without contraction:
+ *   1. at point q of the rule (phi [n_q][nodes_per_cell], w [n_q], weights summing to 1 on the reference cell) an operand with the
+ *      cell's nodal values c is  (phi[q][0]*c[0] + phi[q][1]*c[1]) + phi[q][2]*c[2]  (quadrilaterals: ... + phi[q][3]*c[3]); X and Y
+ *      are the operands whose nodal values are the cell's vertex coordinates
+ *   2. the program gives s_q
+ *   3. from b = 0:  b_i = b_i + (w[q]*phi[q][i])*s_q  for q ascending
+ *   4. the nodal source is the reference cell's mass inverse applied to b (the constant Jacobian cancels):
+ *      triangles  12*b_i - 3*((b_0 + b_1) + b_2);   parallelograms  (16*b_i - 8*(b_(i+1) + b_(i+3))) + 4*b_(i+2), indices mod 4.
+ * Instructions (a, b: the two topmost values, b on top; every leaf pushes one value):
+ *   CONST i   consts[i]                      TRACER j  tracer j: during a stage of tracer `tracer_id` operand TRACER tracer_id is that
+ *   FIELD f   coefficient field of slot f              stage's INPUT buffer, every other tracer its buffer A (already stepped for lower
+ *   X, Y      coordinates                              ids, old for higher ids: the Gauss-Seidel order of swe2d_advance_coupled)
+ *   ADD a + b   SUB a - b   MUL a*b   DIV a/b   NEG -a   ABS |a|   MIN b < a ? b : a   MAX b > a ? b : a
+ *   POWI n    2 <= n <= 16:  r = a;  r = r*a  repeated n - 1 times
+ *   SQRT EXP LOG   the device's math library (SQRT is correctly rounded; EXP and LOG need not round as a host library does)
+ *   LT LE GT GE EQ NE   a op b ? 1.0 : 0.0      AND  a != 0 && b != 0     OR  a != 0 || b != 0     NOT  a == 0   (1.0 / 0.0)
+ *   SELECT    of the three topmost values c, a, b (b on top):  c != 0 ? a : b
+ * A conservative tracer's operand is the stored field q = H*T (and the stage kernel multiplies the source by H as for any source).
+ * Limits: SWE2D_REACTION_MAX_CODE instructions, at most SWE2D_REACTION_MAX_STACK values on the stack at any time (the program is
+ * checked when it is set: no underflow, exactly one value left), SWE2D_REACTION_MAX_CONSTS constants, SWE2D_REACTION_MAX_FIELDS
+ * coefficient fields per handle, SWE2D_REACTION_MAX_TRACERS distinct tracers per program, SWE2D_REACTION_MAX_QUAD points.
+ * Triangles and parallelograms only: SWE2D_ERR_UNSUPPORTED on a handle with general quadrilaterals. */
+#define SWE2D_REACTION_MAX_CODE 64
+#define SWE2D_REACTION_MAX_STACK 8
+#define SWE2D_REACTION_MAX_CONSTS 16
+#define SWE2D_REACTION_MAX_FIELDS 4
+#define SWE2D_REACTION_MAX_TRACERS 8
+#define SWE2D_REACTION_MAX_QUAD 64
+enum swe2d_reaction_op {
+    SWE2D_RX_CONST = 0, SWE2D_RX_TRACER, SWE2D_RX_FIELD, SWE2D_RX_X, SWE2D_RX_Y,
+    SWE2D_RX_ADD, SWE2D_RX_SUB, SWE2D_RX_MUL, SWE2D_RX_DIV, SWE2D_RX_NEG, SWE2D_RX_ABS, SWE2D_RX_MIN, SWE2D_RX_MAX, SWE2D_RX_POWI,
+    SWE2D_RX_SQRT, SWE2D_RX_EXP, SWE2D_RX_LOG,
+    SWE2D_RX_LT, SWE2D_RX_LE, SWE2D_RX_GT, SWE2D_RX_GE, SWE2D_RX_EQ, SWE2D_RX_NE, SWE2D_RX_AND, SWE2D_RX_OR, SWE2D_RX_NOT, SWE2D_RX_SELECT,
+    SWE2D_RX_COUNT
+};
+/* sets (n_code > 0) or removes (n_code = 0: the tracer has no source again) the program of a tracer.  The source planes are allocated
+ * here; an allocation failure names the bytes.  swe2d_tracer_set_source on the tracer replaces the program by the uploaded source. */
+int  swe2d_tracer_set_reaction(swe2d_handle *h, int tracer_id, int32_t n_code, const int32_t *code, int32_t n_const,
+                               const double *consts, int32_t n_q, const double *phi, const double *w);
+/* new values for the constants of the tracer's program (n_const as set) */
+int  swe2d_tracer_set_reaction_constants(swe2d_handle *h, int tracer_id, int32_t n_const, const double *consts);
+/* coefficient field of slot 0 .. SWE2D_REACTION_MAX_FIELDS-1: nodal [n_cells][nodes_per_cell]; NULL frees the slot.  A stage of a
+ * tracer whose program names an empty slot returns SWE2D_ERR_INVALID_ARGUMENT. */
+int  swe2d_reaction_set_field(swe2d_handle *h, int32_t slot, const double *nodal);
+/* synchronises; the tracer's nodal source planes [n_cells][nodes_per_cell] as the last pass (or swe2d_tracer_set_source) left them;
+ * SWE2D_ERR_INVALID_ARGUMENT for a tracer without a source */
+int  swe2d_tracer_get_source(swe2d_handle *h, int tracer_id, double *nodal);
+/* synchronises; tracer buffer i_buffer = 0 (T0 / the step result), 1 or 2 (what stages 0 and 1 wrote) [n_cells][nodes_per_cell]: what
+ * a host evaluation of a reacting source reads between the stages */
+int  swe2d_tracer_get_buffer(swe2d_handle *h, int tracer_id, int i_buffer, double *nodal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ from .meshio import read_gmsh, write_gmsh  # noqa: F401
 from .options import (Constant, ModelOptions2d, TidalTurbineFarmOptions, DiscreteTidalTurbineFarmOptions,  # noqa: F401
                       ConstantTidalTurbineOptions, TabulatedTidalTurbineOptions, TidalTurbineOptions)
 from . import turbines  # noqa: F401
+from . import reactions  # noqa: F401
 from .shallowwater_eq import g_grav, physical_constants, rho_0  # noqa: F401
 
 

@@ -239,6 +239,11 @@ SYMBOLS = {
     'swe2d_particles_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip, _ip, _ip, _ip]),
     'swe2d_particles_read_rows': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip]),
     'swe2d_particles_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_tracer_set_reaction': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int32, _ip, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp]),
+    'swe2d_tracer_set_reaction_constants': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int32, _dp]),
+    'swe2d_reaction_set_field': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
+    'swe2d_tracer_get_source': (ctypes.c_int, [_H, ctypes.c_int, _dp]),
+    'swe2d_tracer_get_buffer': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int, _dp]),
 }
 
 _lib = None

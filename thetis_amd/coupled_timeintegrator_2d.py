@@ -5,6 +5,7 @@ fields of the same C-ABI handle that steps the shallow water equations.
 """
 import numpy as np
 
+from . import reactions
 from .function import Function
 from .log import print_output
 from .options import Constant
@@ -59,7 +60,14 @@ class DeviceTracerSSPRK33(object):
         self.solution._pull_hook = self._pull
         self.solution._device_field = (self, self.tid)
         self._src_signature = None
-        self._push_source()
+        # a source that is an expression of tracer Functions (thetis_amd/reactions.py) is evaluated on the device in front of every
+        # stage.  The tracer steppers are created one after another, so whether a Function operand is a tracer is only known when
+        # the coupled integrator has them all: resolve_reaction, called from there.
+        self._reaction = None
+        self._host_reaction = None
+        self._reaction_pending = reactions.has_function_leaf(fields.get('source-{:}'.format(equation.label)))
+        if not self._reaction_pending:
+            self._push_source()
         if getattr(equation, 'conservative', False):
             self.device.tracer_set_conservative(self.tid, True)
         mu = fields.get('diffusivity_h-{:}'.format(equation.label))
@@ -69,8 +77,71 @@ class DeviceTracerSSPRK33(object):
                                                float(equation.options.sipg_factor_tracer))
         self._push_bcs()
 
+    def _tracer_of(self, f):
+        """tracer id of a Function that is the solution of a tracer on this device; < 0: a field of the flow; None: neither"""
+        df = getattr(f, '_device_field', None)
+        if df is None or getattr(df[0], 'device', None) is not self.device:
+            return None
+        if isinstance(df[1], str):              # 'uv' / 'elev' of the shallow water stepper (rungekutta.py)
+            return -1
+        return int(df[1])
+
+    def resolve_reaction(self):
+        """decide, now that every tracer stepper exists, whether the source reacts; compile it if so"""
+        if not self._reaction_pending:
+            return
+        self._reaction_pending = False
+        src = self.fields.get('source-{:}'.format(self.equation.label))
+        if not reactions.is_reactive(src, self._tracer_of):     # (a flow operand counts: compile_source refuses it by name)
+            self._push_source()                 # today's path: nodal values, once
+            return
+        mesh = self.equation.mesh
+        comm = getattr(self.swe, 'comm', None)
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError('a tracer source that depends on tracers is not available on several ranks (the partitioned '
+                                      'stepper carries no reaction programs)')
+        npc = int(np.asarray(mesh.cells).shape[1])
+        if npc == 4 and not getattr(mesh, 'affine', True):
+            raise NotImplementedError('a tracer source that depends on tracers needs triangles or parallelograms: on a non-affine '
+                                      'quadrilateral mesh the Jacobian varies inside a cell')
+        shared = self.device.__dict__.setdefault('_reaction_fields', [])
+        self._reaction = reactions.compile_source(src, self._tracer_of, npc, shared)
+        shared[:] = self._reaction.fields
+        self._reaction_set = False
+        if not hasattr(self.device, 'tracer_set_reaction'):
+            if not hasattr(self.device, 'tracer_get_buffer'):
+                raise NotImplementedError('a device class without tracer_set_reaction must give the stage buffers of a tracer '
+                                          '(tracer_get_buffer) for the host evaluation of a reacting source')
+            self._host_reaction = reactions.HostReaction(self._reaction, mesh.cell_xy())
+        self._push_source()
+
+    def _host_source(self, i_in):
+        """host fallback: the source of the stage that reads buffer ``i_in``, from the tracers as they are on the device"""
+        vals = {j: self.device.tracer_get_buffer(j, i_in if j == self.tid else 0) for j in self._reaction.tracers}
+        self.device.tracer_set_source(self.tid, self._host_reaction.evaluate(vals))
+
     def _push_source(self):
         """(re-)upload the tracer source when it changed (a Function updated by update_forcings, or a Constant)"""
+        if self._reaction_pending:
+            return
+        if self._reaction is not None:
+            p = self._reaction
+            if self._host_reaction is not None:
+                return                          # evaluated per stage from the live Constants and Functions (_host_source)
+            sig = p.signature()
+            if sig != self._src_signature:
+                seen = self.device.__dict__.setdefault('_reaction_field_versions', {})
+                for slot, f in enumerate(p.fields):
+                    if seen.get(slot) != (id(f), f._host_version):
+                        self.device.reaction_set_field(slot, f.cell_node_values())
+                        seen[slot] = (id(f), f._host_version)
+                if not self._reaction_set:
+                    self.device.tracer_set_reaction(self.tid, p.code, p.constant_values(), p.phi, p.w)
+                    self._reaction_set = True
+                else:
+                    self.device.tracer_set_reaction_constants(self.tid, p.constant_values())
+                self._src_signature = sig
+            return
         src = self.fields.get('source-{:}'.format(self.equation.label))
         sig = self.swe._signature(src)
         if sig != self._src_signature:
@@ -151,6 +222,10 @@ class DeviceTracerSSPRK33(object):
             self._push_source()
         if i_stage == 0:
             self._sync_to_device()
+        if self._reaction is not None:
+            self._push_source()                 # (a Constant of the source may have changed without update_forcings)
+            if self._host_reaction is not None:
+                self._host_source(i_stage)
         self.device.tracer_solve_stage(self.tid, i_stage)
         self._device_ahead = True
 
@@ -174,6 +249,10 @@ class DeviceTracerForwardEuler(DeviceTracerSSPRK33):
             self._push_bcs()
             self._push_source()
         self._sync_to_device()
+        if self._reaction is not None:
+            self._push_source()
+            if self._host_reaction is not None:
+                self._host_source(0)
         self.device.tracer_forward_euler(self.tid)
         self._device_ahead = True
 
@@ -195,6 +274,10 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         o = self.options
         self.device.tracer_set_options(o.use_lax_friedrichs_tracer, float(o.lax_friedrichs_tracer_scaling_factor),
                                        _velocity_factor(o.tracer_advective_velocity_factor))
+        for ts in tracer_steppers.values():     # every tracer has its id now: which sources react (thetis_amd/reactions.py)
+            ts.resolve_reaction()
+        self.reacting = [ts for ts in tracer_steppers.values() if ts._reaction is not None]
+        self.host_reactions = any(ts._host_reaction is not None for ts in self.reacting)
 
     def set_dt(self, dt):
         for stepper in sorted(self.timesteppers):
@@ -209,11 +292,14 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
     def advance(self, t, update_forcings=None):
         """coupled_timeintegrator_2d.py:93-113"""
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
-        fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
+        # (a reacting source the HOST evaluates needs the tracers between the stages: stage by stage)
+        fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3 and not self.host_reactions
         if update_forcings is None and fused and not self.swe.forced_per_stage:        # all SSPRK33: one C call per time step
             self.swe._sync_to_device()
             for ts in self.tracers.values():
                 ts._sync_to_device()
+            for ts in self.reacting:
+                ts._push_source()               # (a changed Constant of a program)
             self.swe._tide_clock(t)
             self.device.advance_coupled(1, tracer_only=self.options.tracer_only, use_limiter=use_limiter)
             self.swe._device_ahead = True
@@ -224,6 +310,9 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             self.swe.advance(t, update_forcings=update_forcings)
         else:
             self.swe._sync_to_device()
+        if self.reacting:                       # a reacting source reads the OTHER tracers on the device
+            for ts in self.tracers.values():
+                ts._sync_to_device()
         for label, ts in self.tracers.items():
             ts.advance(t, update_forcings=update_forcings)
             if use_limiter:
@@ -242,7 +331,7 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         sets of the device that take one row after every step (FlowSolver2d.create_iterator).  ``clock`` = (t_start, n_done) of
         the time loop, for a tide the device evaluates (SSPRK33.advance_steps)."""
         use_limiter = self.options.use_limiter_for_tracers and self.options.polynomial_degree > 0
-        fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3
+        fused = all(ts.n_stages == 3 for ts in self.tracers.values()) and self.swe.n_stages == 3 and not self.host_reactions
         if not fused:
             done = [0]
 
@@ -257,6 +346,8 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         for ts in self.tracers.values():
             ts._sync_to_device()
         self.swe._tide_clock(*(clock if clock is not None else (t, 0)))
+        for ts in self.reacting:
+            ts._push_source()
         if probes:
             advance_with_rows(self.device, n_steps,
                               lambda j: self.device.advance_coupled(j, tracer_only=self.options.tracer_only, use_limiter=use_limiter),

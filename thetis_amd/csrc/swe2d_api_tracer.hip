@@ -40,6 +40,8 @@ int launch_tracer_stage(Handle *h, int id, int in, int out, double a0, double a1
 {
     if (c1 <= c0) return SWE2D_OK;
     Handle::Tracer &t = h->tracers[id];
+    // a reacting tracer: its source planes from the current tracer values first (swe2d_reaction.hip)
+    if (t.rx.n_code > 0) { if (int rc = reaction_launch(h, id, in, c0, c1)) return rc; }
     SweTracerArgs a;
     fill_tracer_args(h, id, a, in, out, a0, a1, beta, c0, c1, mean_out);
     // triangles: cell integral and interior facets of the diffusion inside the stage kernel, boundary facets by a launch
@@ -349,6 +351,7 @@ int swe2d_tracer_set_source(swe2d_handle *hh, int id, const double *nodal)
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     Handle::Tracer &t = h->tracers[id];
+    t.rx.n_code = 0;                                    // (an uploaded source replaces a reaction program)
     if (!nodal) {
         if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }
         return SWE2D_OK;

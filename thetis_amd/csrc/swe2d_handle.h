@@ -225,8 +225,19 @@ struct Handle {
         double mu_const = 0.0, sipg_factor = 1.0;
         int bc_diff_kind[SWE_MAX_MARKERS];
         double bc_diff_flux[SWE_MAX_MARKERS];
+        // reaction program (swe2d_reaction.hip): n_code > 0 = a pass in front of every stage launch writes `source`
+        struct Reaction {
+            int n_code = 0, n_const = 0, n_q = 0, n_tracers = 0;
+            int code[SWE2D_REACTION_MAX_CODE] = {0};            // as launched: the arg of TRACER / FIELD is a slot of the operand table
+            double consts[SWE2D_REACTION_MAX_CONSTS] = {0.0};
+            int tracer_ids[SWE2D_REACTION_MAX_TRACERS] = {0};   // operand slot -> tracer id
+            unsigned field_mask = 0u;                           // coefficient slots the program names
+            double phi[SWE2D_REACTION_MAX_QUAD*4] = {0.0}, w[SWE2D_REACTION_MAX_QUAD] = {0.0};
+        };
+        Reaction rx;
     };
     std::vector<Tracer> tracers;
+    double *rx_field[SWE2D_REACTION_MAX_FIELDS] = {nullptr, nullptr, nullptr, nullptr};   // coefficient fields of the reaction programs, npc planes
     int tracer_use_lf = 0;
     double tracer_lf_factor = 1.0, tracer_vel_factor = 1.0;
     std::vector<int> host_cells;                 // [n][3] vertex ids as given (limiter default topology)
@@ -459,6 +470,9 @@ int atm_check_advance(Handle *h, int n_steps, bool forward_euler);   // SWE2D_ER
 void stats_free_all(Handle *h);
 // ---- Lagrangian particles (swe2d_particles.hip): frees every particle set of the handle (swe2d_destroy)
 void particles_free_all(Handle *h);
+// ---- reacting tracers (swe2d_reaction.hip)
+int reaction_launch(Handle *h, int id, int in, int c0, int c1);   // in front of a stage launch of tracer `id` reading buffer `in`: its source planes on [c0, c1)
+void reaction_free_all(Handle *h);                      // frees the coefficient fields (swe2d_destroy)
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -934,6 +934,42 @@ class Swe2dDevice(object):
             a = self._nodal_in(np.broadcast_to(np.asarray(nodal, dtype=np.float64), (self.n_cells, self.npc)))
             self._ck(self.lib.swe2d_tracer_set_source(self.h, tid, _ptr(a)))
 
+    # -- reacting tracers (thetis_amd/reactions.py, csrc/swe2d_reaction.hip)
+    def tracer_set_reaction(self, tid, code, consts=(), phi=None, w=None):
+        """the source program of a tracer (``code`` None or empty: removes it, the tracer has no source again)"""
+        ip = ctypes.POINTER(ctypes.c_int32)
+        if code is None or len(code) == 0:
+            self._ck(self.lib.swe2d_tracer_set_reaction(self.h, int(tid), 0, None, 0, None, 0, None, None))
+            return
+        code = np.ascontiguousarray(code, dtype=np.int32)
+        consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if phi.shape != (w.size, self.npc):
+            raise ValueError('phi must be (n_q, nodes per cell)')
+        self._ck(self.lib.swe2d_tracer_set_reaction(self.h, int(tid), code.size, code.ctypes.data_as(ip), consts.size,
+                                                    _ptr(consts) if consts.size else None, w.size, _ptr(phi), _ptr(w)))
+
+    def tracer_set_reaction_constants(self, tid, consts):
+        consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+        self._ck(self.lib.swe2d_tracer_set_reaction_constants(self.h, int(tid), consts.size, _ptr(consts) if consts.size else None))
+
+    def reaction_set_field(self, slot, nodal):
+        """coefficient field of a reaction program: (N, k) values at the nodes of every cell; None frees the slot"""
+        self._ck(self.lib.swe2d_reaction_set_field(self.h, int(slot), None if nodal is None else _ptr(self._nodal_in(nodal))))
+
+    def tracer_get_source(self, tid):
+        """the nodal source of a tracer as the last reaction pass (or ``tracer_set_source``) left it"""
+        a = np.empty((self.n_cells, self.npc))
+        self._ck(self.lib.swe2d_tracer_get_source(self.h, int(tid), _ptr(a)))
+        return self._nodal_out(a)
+
+    def tracer_get_buffer(self, tid, i_buffer):
+        """tracer buffer 0 (T0 / the step result), 1 or 2 (what stages 0 and 1 wrote)"""
+        a = np.empty((self.n_cells, self.npc))
+        self._ck(self.lib.swe2d_tracer_get_buffer(self.h, int(tid), int(i_buffer), _ptr(a)))
+        return self._nodal_out(a)
+
     def tracer_solve_stage(self, tid, i_stage):
         self._ck(self.lib.swe2d_tracer_solve_stage(self.h, tid, int(i_stage)))
 

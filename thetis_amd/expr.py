@@ -76,12 +76,22 @@ def _value(a, x, y):
     return a
 
 
+# names of the numpy functions in an expression's node
+_OP_NAMES = {np.add: 'add', np.subtract: 'sub', np.multiply: 'mul', np.divide: 'div', np.power: 'pow', np.less: 'lt',
+             np.less_equal: 'le', np.greater: 'gt', np.greater_equal: 'ge', np.equal: 'eq', np.not_equal: 'ne',
+             np.logical_and: 'and', np.logical_or: 'or', np.maximum: 'max', np.minimum: 'min', np.sin: 'sin', np.cos: 'cos',
+             np.tan: 'tan', np.exp: 'exp', np.sqrt: 'sqrt', np.tanh: 'tanh', np.cosh: 'cosh', np.sinh: 'sinh', np.log: 'ln',
+             np.sign: 'sign', np.abs: 'abs'}
+
+
 class Expr(object):
     """A lazy scalar (or 2-vector) expression of the spatial coordinates: ``expr(x, y)`` evaluates it on arrays."""
     __array_priority__ = 1000            # numpy scalars / arrays on the left defer to the reflected operators below
 
-    def __init__(self, fn, vector=False):
-        self._fn, self.vector = fn, vector
+    def __init__(self, fn, vector=False, node=None):
+        # node: (op, operands) - the structure of the expression next to its lambda (thetis_amd/reactions.py compiles it; evaluation
+        # never looks at it).  Operands are Exprs, numbers, Constants and Functions; 'x' / 'y' / 'function' are the leaves.
+        self._fn, self.vector, self.node = fn, vector, node
 
     def __call__(self, x, y):
         return self._fn(np.asarray(x, dtype=float), np.asarray(y, dtype=float))
@@ -89,7 +99,7 @@ class Expr(object):
     # -- arithmetic
     def _bin(self, other, op, reflected=False):
         a, b = (other, self) if reflected else (self, other)
-        return Expr(lambda x, y: op(_value(a, x, y), _value(b, x, y)))
+        return Expr(lambda x, y: op(_value(a, x, y), _value(b, x, y)), node=(_OP_NAMES[op], (a, b)))
 
     def __add__(self, o): return self._bin(o, np.add)
     def __radd__(self, o): return self._bin(o, np.add, True)
@@ -101,9 +111,9 @@ class Expr(object):
     def __rtruediv__(self, o): return self._bin(o, np.divide, True)
     def __pow__(self, o): return self._bin(o, np.power)
     def __rpow__(self, o): return self._bin(o, np.power, True)
-    def __neg__(self): return Expr(lambda x, y: -self(x, y))
+    def __neg__(self): return Expr(lambda x, y: -self(x, y), node=('neg', (self,)))
     def __pos__(self): return self
-    def __abs__(self): return Expr(lambda x, y: np.abs(self(x, y)))
+    def __abs__(self): return Expr(lambda x, y: np.abs(self(x, y)), node=('abs', (self,)))
 
     # -- comparisons give conditions (boolean expressions) for conditional()
     def __lt__(self, o): return self._bin(o, np.less)
@@ -114,7 +124,7 @@ class Expr(object):
     def __getitem__(self, i):
         if not self.vector:
             raise TypeError('a scalar expression has no components')
-        return Expr(lambda x, y: self(x, y)[int(i)])
+        return Expr(lambda x, y: self(x, y)[int(i)], node=('component', (self, int(i))))
 
     def __bool__(self):
         raise TypeError('the truth value of an expression is not defined: use conditional(cond, a, b), And, Or, Not')
@@ -122,24 +132,25 @@ class Expr(object):
 
 def SpatialCoordinate(mesh=None):
     """``x, y = SpatialCoordinate(mesh2d)``"""
-    return Expr(lambda x, y: x), Expr(lambda x, y: y)
+    return Expr(lambda x, y: x, node=('x', ())), Expr(lambda x, y: y, node=('y', ()))
 
 
 def conditional(cond, true_value, false_value):
-    return Expr(lambda x, y: np.where(_value(cond, x, y), _value(true_value, x, y), _value(false_value, x, y)))
+    return Expr(lambda x, y: np.where(_value(cond, x, y), _value(true_value, x, y), _value(false_value, x, y)),
+                node=('conditional', (cond, true_value, false_value)))
 
 
 def as_vector(components):
     c = tuple(components)
     if len(c) != 2:
         raise NotImplementedError('2D: as_vector((u, v))')
-    return Expr(lambda x, y: (_value(c[0], x, y)*np.ones_like(x), _value(c[1], x, y)*np.ones_like(x)), vector=True)
+    return Expr(lambda x, y: (_value(c[0], x, y)*np.ones_like(x), _value(c[1], x, y)*np.ones_like(x)), vector=True, node=('vector', c))
 
 
 def _unary(f):
     def g(a):
         if isinstance(a, (Expr, Constant)) or hasattr(a, 'dat'):
-            return Expr(lambda x, y: f(_value(a, x, y)))
+            return Expr(lambda x, y: f(_value(a, x, y)), node=(_OP_NAMES[f], (a,)))
         return f(a)
     g.__name__ = f.__name__
     return g
@@ -153,7 +164,7 @@ abs_value = _unary(np.abs)
 
 def _binary(f):
     def g(a, b):
-        return Expr(lambda x, y: f(_value(a, x, y), _value(b, x, y)))
+        return Expr(lambda x, y: f(_value(a, x, y), _value(b, x, y)), node=(_OP_NAMES[f], (a, b)))
     return g
 
 
@@ -163,4 +174,4 @@ max_value, min_value = _binary(np.maximum), _binary(np.minimum)
 
 
 def Not(a):
-    return Expr(lambda x, y: np.logical_not(_value(a, x, y)))
+    return Expr(lambda x, y: np.logical_not(_value(a, x, y)), node=('not', (a,)))

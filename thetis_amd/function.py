@@ -171,7 +171,7 @@ class Function(object):
     # -- a Function inside an expression (thetis_amd/expr.py): lazy, evaluated on the nodes it lives on
     def _expr(self):
         from .expr import Expr, _value
-        return Expr(lambda x, y: _value(self, x, y))
+        return Expr(lambda x, y: _value(self, x, y), node=('function', (self,)))
 
     def __add__(self, o): return self._expr() + o
     def __radd__(self, o): return o + self._expr()

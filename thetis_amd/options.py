@@ -50,6 +50,22 @@ class Constant(object):
     def __repr__(self):
         return 'Constant({:})'.format(self._value)
 
+    # -- a Constant inside an expression (thetis_amd/expr.py): lazy, its value is read when the expression is evaluated
+    def _expr(self):
+        from .expr import Expr, _value
+        return Expr(lambda x, y: _value(self, x, y), node=('constant', (self,)))
+
+    def __add__(self, o): return self._expr() + o
+    def __radd__(self, o): return o + self._expr()
+    def __sub__(self, o): return self._expr() - o
+    def __rsub__(self, o): return o - self._expr()
+    def __mul__(self, o): return self._expr()*o
+    def __rmul__(self, o): return o*self._expr()
+    def __truediv__(self, o): return self._expr()/o
+    def __rtruediv__(self, o): return o/self._expr()
+    def __pow__(self, o): return self._expr()**o
+    def __neg__(self): return -self._expr()
+
 
 # ---- validators ----------------------------------------------------------------------------------------------------
 def _positive_float(name, v):

@@ -27,7 +27,7 @@ def exercise():
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
         for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'atm', 'stats',
-                        'stats+wetting-drying', 'particles', 'particles+wetting-drying'):
+                        'stats+wetting-drying', 'particles', 'particles+wetting-drying', 'reactions'):
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
             bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') or variant == 'dfarm' else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
@@ -201,6 +201,58 @@ def exercise():
                 dev.advance_coupled(2)
                 dev.tracer_diagnostics(tid)
                 n_launch += 20
+            if variant == 'reactions':
+                # reacting tracers: swe_reaction_kernel reads the nodal planes of every tracer and coefficient field its program names
+                # and, for X / Y, the cell vertices and vertex coordinates, and writes the source planes of its tracer through the
+                # checked accesses, one launch in front of every tracer stage launch below (program, constants and rule: kernel
+                # arguments / a buffer the runtime copies).  Gray-Scott with its 9-point rule, then a program with coordinates and
+                # two coefficient fields under the 64-point rule; whole-mesh stages, ragged sub-ranges, ForwardEuler and the batch.
+                # General quadrilaterals: the program is refused.
+                from thetis_amd import Constant, Function, SpatialCoordinate, get_functionspace, reactions
+                from thetis_amd.function import farm_quadrature
+                P1, P1DG = get_functionspace(mesh, 'CG', 1), get_functionspace(mesh, 'DG', 1)
+                fa, fb, fc, fd = Function(P1DG), Function(P1DG), Function(P1), Function(P1DG)
+                rng = np.random.default_rng(10)
+                for f in (fc, fd):
+                    f.assign(rng.uniform(0.5, 1.5, size=f.dat.data_ro.shape))
+                for t in range(2):
+                    assert dev.add_tracer() == t
+                    dev.tracer_set_state(t, rng.uniform(0.2, 1.0, size=(mesh.num_cells, k)))
+                tracer_of = lambda f: 0 if f is fa else (1 if f is fb else None)   # noqa: E731
+                g, kap = Constant(0.024), Constant(0.06)
+                xs, ys = SpatialCoordinate(mesh)
+                span = float(np.abs(cxy).max())
+                pairs = [(g - fa*fb**2 - g*fa, fa*fb**2 - (g + kap)*fb),
+                         (0.01*fc*fa*xs/span - 0.01*fd*fb, 0.01*fd*fb*ys/span - 0.01*fc*fa)]
+                if k == 4 and not getattr(mesh, 'affine', True):
+                    try:
+                        dev.tracer_set_reaction(0, [1], [], *farm_quadrature(4, 2))     # (TRACER 0)
+                        raise AssertionError('a reaction program on general quadrilaterals')
+                    except _lib.Swe2dError as e:
+                        assert e.code == _lib.ERR_UNSUPPORTED
+                else:
+                    third = mesh.num_cells//3 + 1
+                    for j, pair in enumerate(pairs):
+                        shared = []
+                        for t, src in enumerate(pair):
+                            p = reactions.compile_source(src, tracer_of, k, shared)
+                            shared[:] = p.fields
+                            if j == 1:
+                                p.phi, p.w = farm_quadrature(k, 14)
+                            for slot, f in enumerate(p.fields):
+                                dev.reaction_set_field(slot, f.cell_node_values())
+                            dev.tracer_set_reaction(t, p.code, p.constant_values(), p.phi, p.w)
+                        for t in range(2):
+                            for i in range(3):
+                                dev.tracer_solve_stage(t, i)
+                            for i in range(3):
+                                dev.tracer_solve_stage_cells(t, i, 0, third)
+                                dev.tracer_solve_stage_cells(t, i, third, mesh.num_cells)
+                            dev.tracer_forward_euler(t)
+                            assert np.isfinite(dev.tracer_get_source(t)).all() and np.abs(dev.tracer_get_source(t)).max() > 0.0
+                        dev.advance_coupled(2, tracer_only=False, use_limiter=True)
+                        assert all(np.isfinite(dev.tracer_get_state(t)).all() for t in range(2)), (name, variant, j)
+                        n_launch += 2*(3 + 6 + 1 + 6)*2
             dev.advance(2)
             dev.advance_forward_euler(1)
             for i in range(3):                      # sub-range launches with ragged ends
