@@ -772,6 +772,74 @@ int  swe2d_tracer_get_source(swe2d_handle *h, int tracer_id, double *nodal);
  * a host evaluation of a reacting source reads between the stages */
 int  swe2d_tracer_get_buffer(swe2d_handle *h, int tracer_id, int i_buffer, double *nodal);
 
+/* ---- Suspended sediment and Exner bed evolution (triangles, whole meshes, no wetting-drying).
+ * One tracer of the handle is the sediment field S (conservative form: q = H*S).  Its source is not uploaded: a pass in front of every
+ * stage launch of that tracer writes it from three sets of nodal planes - erosion flux E, deposition coefficient D, equilibrium
+ * concentration - that swe2d_sediment_update evaluates from buffer A, ONCE per time step (frozen over the stages, as the reference's
+ * SedimentModel.update(), coupled_timeintegrator_2d.py:100-135).
+ * Closures (thetis/sediment_model.py:136-211), evaluated at the three DG nodes of a cell from that cell's own nodal (u, v) and
+ * H = eta + bathymetry (linear equations: H = bathymetry) - the reference projects uv and H into CG-P1 first; this is the stated
+ * difference.  With the parameters below, every comparison a select:
+ *   U2 = u*u + v*v;  hc = max(H, 0.001);  qfc = 2/(log(max(11.036*hc/ks, 1.001))/kappa)^2
+ *   cfactor = H > ksp ? 2/((1/kappa)*log(11.036*H/ksp))^2 : 0;  mu = qfc > 0 ? cfactor/qfc : 0
+ *   B = a > H ? 1 : a/H;  ustar = sqrt(0.5*qfc*U2);  rouse = ws/(kappa*ustar) - 1;  rm = min(rouse, 3)
+ *   step = |rouse| > 1e-4 ? B*(1 - pow(B, rm))/rm : -B*log(B);  integrated_rouse = max(step > 1e-12 ? 1/step : 1e12, 1)
+ *   tau = rho0*0.5*qfc*U2*mu;  T = tau > 0 ? (tau - taucr)/taucr : -1;  T15 = T > 0 ? T*sqrt(T) : 0
+ *   E = ws*(erosion_factor*T15);  D = ws*integrated_rouse;  equilibrium = E/D
+ * log / pow / sqrt are the device's math library.  The remaining passes are + - * / in the order written, without contraction:
+ *   source (per stage, S the stage's input buffer, H from buffer A and the current bed):   s = (E - D*S)/H;  conservative  s = E - (D*q)/H
+ *     - the nodal interpolant of the reference's erosion and deposition terms (sediment_eq_2d.py:84-104), not their projection
+ *   'equilibrium' boundary (with the update): the per-facet value table of the tracer (swe2d_tracer_set_bc_facets) takes, on the
+ *     facets of the markers set by swe2d_sediment_set_equilibrium_bc, the cell's own equilibrium value at each of its nodes -
+ *     conservative form: times that node's H (the inner depth: the reference's value for a boundary dict without 'elev')
+ *   Exner (swe2d_exner_step, lumped CG-P1 form of exner_eq.py:68-84; bathymetry positive downwards, erosion deepens): per vertex v,
+ *     over its (cell c, local node i) pairs in ascending cell order, j = (i+1)%3, k = (i+2)%3, r = E - D*S [conservative E - (D*q)/H]:
+ *       num = num + (A_c/12)*((2*r_i + r_j) + r_k);   den = den + A_c/3;   A_c = 0.5*|(x1-x0)*(y2-y0) - (x2-x0)*(y1-y0)|
+ *       b_v = b_v + ((dt*fac)*num)/den
+ *     A vertex where min over its nodes of (eta + new b) [linear equations: new b] falls below min_depth keeps its bed and is counted
+ *     (swe2d_exner_skipped).  A right-hand side that does not depend on the bed and a lumped mass: ForwardEuler and SSPRK33 are
+ *     this same single update.
+ * swe2d_advance_coupled steps, per time step: the flow, every other tracer, swe2d_sediment_update, the three sediment stages, the
+ * limiter, and with solve_exner the bed update.  The dataflow kernel, which batches steps, declines a handle with solve_exner. */
+typedef struct swe2d_sediment_params {
+    double ws;               /* settling velocity */
+    double dstar;            /* dimensionless grain size (carried for reference; erosion_factor holds its power) */
+    double taucr;            /* critical bed shear stress */
+    double a;                /* bed_reference_height/2 */
+    double ksp;              /* grain roughness 3*d50 */
+    double ks;               /* bed_reference_height */
+    double rho0;
+    double kappa;            /* von Karman */
+    double fac;              /* morphological_acceleration_factor/(1 - porosity) */
+    double erosion_factor;   /* 0.015*(d50/a)/dstar^0.3 */
+    double min_depth;        /* floor of the depth in the Exner update, > 0 */
+    int32_t conservative;    /* the tracer holds q = H*S */
+    int32_t solve_exner;     /* swe2d_advance_coupled updates the bed after the sediment step */
+} swe2d_sediment_params;
+/* makes tracer `tracer_id` the sediment field (allocates its source planes, the coefficient planes and the Exner tables; sets the
+ * tracer's conservative flag).  The tracer must have neither an uploaded source nor a reaction program (SWE2D_ERR_INVALID_ARGUMENT);
+ * while it is the sediment field swe2d_tracer_set_source and swe2d_tracer_set_reaction on it are refused (removing: no-ops), and
+ * swe2d_sediment_clear gives back a plain tracer without a source in the non-conservative form.  SWE2D_ERR_UNSUPPORTED: quadrilaterals, partitions, wetting-drying, solve_exner with turbine farms. */
+int  swe2d_sediment_set(swe2d_handle *h, int tracer_id, const swe2d_sediment_params *par);
+/* marker slot 1 .. SWE2D_MAX_MARKERS-1 of the sediment tracer carries 'equilibrium' (on = 0: no longer) */
+int  swe2d_sediment_set_equilibrium_bc(swe2d_handle *h, int marker, int on);
+/* E, D, equilibrium from buffer A and the current bed; the 'equilibrium' facets of the value table (asynchronous) */
+int  swe2d_sediment_update(swe2d_handle *h);
+/* synchronises; the planes as nodal [n_cells][3]; any pointer may be NULL */
+int  swe2d_sediment_read(swe2d_handle *h, double *erosion, double *deposition, double *equilibrium);
+/* synchronises; the sediment tracer's per-facet value table [facet 3][n_cells][node 3] */
+int  swe2d_sediment_read_bc(swe2d_handle *h, double *facet_nodal);
+/* the tracer is a plain tracer without a source again; the tables are freed */
+int  swe2d_sediment_clear(swe2d_handle *h);
+/* one bed update from the sediment tracer's buffer A with the handle's dt (asynchronous) */
+int  swe2d_exner_step(swe2d_handle *h);
+/* synchronises; vertices left unchanged by the bed updates since swe2d_sediment_set */
+int  swe2d_exner_skipped(swe2d_handle *h, int64_t *n_skipped);
+/* synchronises; the bathymetry [n_vertices] as the kernels read it */
+int  swe2d_get_bathymetry(swe2d_handle *h, double *vertex_values);
+/* synchronises; replaces the bathymetry [n_vertices] (every kernel reads it at launch).  SWE2D_ERR_UNSUPPORTED with wetting-drying */
+int  swe2d_set_bathymetry(swe2d_handle *h, const double *vertex_values);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,9 @@ from .options import (Constant, ModelOptions2d, TidalTurbineFarmOptions, Discret
                       ConstantTidalTurbineOptions, TabulatedTidalTurbineOptions, TidalTurbineOptions)
 from . import turbines  # noqa: F401
 from . import reactions  # noqa: F401
+from . import sediment_model  # noqa: F401
+from .options import SedimentModelOptions  # noqa: F401
+from .sediment_model import SedimentModel  # noqa: F401
 from .shallowwater_eq import g_grav, physical_constants, rho_0  # noqa: F401
 
 

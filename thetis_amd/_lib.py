@@ -101,6 +101,14 @@ class TurbineParams(ctypes.Structure):
                 ('power', ctypes.c_double*MAX_THRUST_TABLE)]
 
 
+class SedimentParams(ctypes.Structure):
+    """include/swe2d.h swe2d_sediment_params"""
+    _fields_ = [('ws', ctypes.c_double), ('dstar', ctypes.c_double), ('taucr', ctypes.c_double), ('a', ctypes.c_double),
+                ('ksp', ctypes.c_double), ('ks', ctypes.c_double), ('rho0', ctypes.c_double), ('kappa', ctypes.c_double),
+                ('fac', ctypes.c_double), ('erosion_factor', ctypes.c_double), ('min_depth', ctypes.c_double),
+                ('conservative', ctypes.c_int32), ('solve_exner', ctypes.c_int32)]
+
+
 # every symbol include/swe2d.h declares: name -> (restype, argtypes)
 _H = ctypes.c_void_p
 SYMBOLS = {
@@ -244,6 +252,16 @@ SYMBOLS = {
     'swe2d_reaction_set_field': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),
     'swe2d_tracer_get_source': (ctypes.c_int, [_H, ctypes.c_int, _dp]),
     'swe2d_tracer_get_buffer': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int, _dp]),
+    'swe2d_sediment_set': (ctypes.c_int, [_H, ctypes.c_int, ctypes.POINTER(SedimentParams)]),
+    'swe2d_sediment_set_equilibrium_bc': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int]),
+    'swe2d_sediment_update': (ctypes.c_int, [_H]),
+    'swe2d_sediment_read': (ctypes.c_int, [_H, _dp, _dp, _dp]),
+    'swe2d_sediment_read_bc': (ctypes.c_int, [_H, _dp]),
+    'swe2d_sediment_clear': (ctypes.c_int, [_H]),
+    'swe2d_exner_step': (ctypes.c_int, [_H]),
+    'swe2d_exner_skipped': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_get_bathymetry': (ctypes.c_int, [_H, _dp]),
+    'swe2d_set_bathymetry': (ctypes.c_int, [_H, _dp]),
 }
 
 _lib = None

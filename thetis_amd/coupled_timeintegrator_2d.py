@@ -12,7 +12,8 @@ from .options import Constant
 from .rungekutta import advance_with_rows
 from .timeintegrator import TimeIntegratorBase
 
-__all__ = ['DeviceTracerSSPRK33', 'DeviceTracerForwardEuler', 'GeneralCoupledTimeIntegrator2D']
+__all__ = ['DeviceTracerSSPRK33', 'DeviceTracerForwardEuler', 'DeviceSedimentSSPRK33', 'DeviceSedimentForwardEuler',
+           'GeneralCoupledTimeIntegrator2D']
 
 
 def _velocity_factor(f):
@@ -196,6 +197,9 @@ class DeviceTracerSSPRK33(object):
                     kind, dfl = (4 if is_field else 2), 0.0
                 self.device.tracer_set_diffusion_bc(self.tid, marker, kind, dfl)
 
+    def _before_stage(self, i_in):
+        """in front of the stage launch that reads buffer ``i_in`` (the sediment stepper's host fallback writes its source here)"""
+
     def _pull(self):
         if self._device_ahead:
             self.solution._data[...] = self.device.tracer_get_state(self.tid).reshape(self.solution._data.shape)
@@ -226,6 +230,7 @@ class DeviceTracerSSPRK33(object):
             self._push_source()                 # (a Constant of the source may have changed without update_forcings)
             if self._host_reaction is not None:
                 self._host_source(i_stage)
+        self._before_stage(i_stage)
         self.device.tracer_solve_stage(self.tid, i_stage)
         self._device_ahead = True
 
@@ -253,8 +258,108 @@ class DeviceTracerForwardEuler(DeviceTracerSSPRK33):
             self._push_source()
             if self._host_reaction is not None:
                 self._host_source(0)
+        self._before_stage(0)
         self.device.tracer_forward_euler(self.tid)
         self._device_ahead = True
+
+
+class _SedimentStepper(object):
+    """The sediment field as one more device tracer (thetis/sediment_eq_2d.py): its source comes from the sediment model's planes
+    in front of every stage (csrc/swe2d_sediment.hip), and a marker with ``'equilibrium'`` takes its outer value from the model."""
+    sediment_model = None
+
+    host_sediment = False
+
+    def attach_sediment(self, model):
+        """``model`` becomes this tracer's source.  A device class with the sediment calls runs the passes itself; one without
+        them gets them from the host replay (``HostSediment``), as the reaction and particle passes do: the source per stage from the
+        stage's input buffer, the 'equilibrium' values per step through the per-facet table, the Exner update through
+        ``set_bathymetry`` - one transfer of the field per stage and of the flow per step."""
+        self.sediment_model = model
+        if hasattr(self.device, 'sediment_set'):
+            model.bind_device(self.device, self.tid)
+        else:
+            need = ['tracer_get_buffer', 'tracer_set_bc_facets']
+            if self.equation.options.sediment_model_options.solve_exner:
+                need.append('set_bathymetry')
+            missing = [n for n in need if not hasattr(self.device, n)]
+            if missing:
+                raise NotImplementedError('sediment_model_options: a device class without the sediment passes must give {:} for the '
+                                          'host evaluation'.format(', '.join(missing)))
+            self.host_sediment = True
+        self._push_bcs()
+
+    def sediment_update(self):
+        """the model on the current flow, once per time step; host fallback: the 'equilibrium' facets as well"""
+        self.sediment_model.update()
+        if self.host_sediment:
+            self._push_host_equilibrium()
+
+    def _host_fields(self):
+        m = self.sediment_model
+        return m.elev.cell_node_values(), m._bathymetry()
+
+    def _push_host_equilibrium(self):
+        m = self.sediment_model
+        if m._planes is None:
+            return
+        eta, bath = self._host_fields()
+        vals = m.host.boundary_values(m._planes[2], eta, bath)
+        for marker in self.equation.mesh.boundary_markers:
+            if 'equilibrium' in (self.bnd_conditions.get(marker) or {}):
+                slot = self.device._slot(marker)
+                cells, _ = self.device.boundary_facets(slot)
+                self.device.tracer_set_bc_facets(self.tid, slot, vals[cells])
+                if self.diffusive:
+                    self.device.tracer_set_diffusion_bc(self.tid, marker, 4, 0.0)
+
+    def _before_stage(self, i_in):
+        if not self.host_sediment:
+            return
+        m = self.sediment_model
+        E, D, _ = m._terms()
+        eta, bath = self._host_fields()
+        self.device.tracer_set_source(self.tid, m.host.source(E, D, self.device.tracer_get_buffer(self.tid, i_in), eta, bath))
+
+    def exner_step(self, solver):
+        """the bed update after the sediment step (and limiter)"""
+        if not self.host_sediment:
+            self.device.exner_step()
+            return
+        m = self.sediment_model
+        E, D, _ = m._terms()
+        eta, bath = self._host_fields()
+        new = m.host.exner(E, D, self.device.tracer_get_state(self.tid), eta, bath, self.dt)
+        self.device.set_bathymetry(new)
+        b = solver.fields.bathymetry_2d
+        b._data[...] = new.reshape(b._data.shape)
+        b._host_version += 1
+
+    def _push_bcs(self):
+        full = self.bnd_conditions
+        self.bnd_conditions = {m: (None if f is None else {k: v for k, v in f.items() if k != 'equilibrium'}) for m, f in full.items()}
+        try:
+            super(_SedimentStepper, self)._push_bcs()
+        finally:
+            self.bnd_conditions = full
+        if self.sediment_model is None:
+            return
+        if self.host_sediment:
+            self._push_host_equilibrium()
+            return
+        for marker in self.equation.mesh.boundary_markers:
+            eq = 'equilibrium' in (full.get(marker) or {})
+            self.device.sediment_set_equilibrium_bc(marker, eq)
+            if eq and self.diffusive:           # the diffusion operator's boundary term reads the same per-facet table
+                self.device.tracer_set_diffusion_bc(self.tid, marker, 4, 0.0)
+
+
+class DeviceSedimentSSPRK33(_SedimentStepper, DeviceTracerSSPRK33):
+    pass
+
+
+class DeviceSedimentForwardEuler(_SedimentStepper, DeviceTracerForwardEuler):
+    pass
 
 
 class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
@@ -278,6 +383,8 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             ts.resolve_reaction()
         self.reacting = [ts for ts in tracer_steppers.values() if ts._reaction is not None]
         self.host_reactions = any(ts._host_reaction is not None for ts in self.reacting)
+        # (a sediment field the HOST evaluates needs the stage buffers as well: stage by stage)
+        self.host_reactions = self.host_reactions or any(getattr(ts, 'host_sediment', False) for ts in tracer_steppers.values())
 
     def set_dt(self, dt):
         for stepper in sorted(self.timesteppers):
@@ -298,6 +405,8 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             self.swe._sync_to_device()
             for ts in self.tracers.values():
                 ts._sync_to_device()
+                if getattr(ts, 'sediment_model', None) is not None:
+                    ts.sediment_model._planes = None      # (the batch refreshes the planes on the device)
             for ts in self.reacting:
                 ts._push_source()               # (a changed Constant of a program)
             self.swe._tide_clock(t)
@@ -305,6 +414,7 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             self.swe._device_ahead = True
             for ts in self.tracers.values():
                 ts._device_ahead = True
+            self._bed_moved()
             return
         if not self.options.tracer_only:
             self.swe.advance(t, update_forcings=update_forcings)
@@ -314,9 +424,18 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             for ts in self.tracers.values():
                 ts._sync_to_device()
         for label, ts in self.tracers.items():
+            # the sediment field comes last (coupled_timeintegrator_2d.py:100-135): the model on the new flow, its coefficients
+            # frozen over the step, the sediment stages, the limiter, the Exner update
+            sed = getattr(ts, 'sediment_model', None)
+            if sed is not None:
+                ts._sync_to_device()
+                ts.sediment_update()
             ts.advance(t, update_forcings=update_forcings)
             if use_limiter:
                 self.device.tracer_limit(ts.tid)
+            if sed is not None and self.options.sediment_model_options.solve_exner:
+                ts.exner_step(self.solver)
+                self._bed_moved()
 
     @property
     def forced_per_stage(self):
@@ -357,6 +476,16 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         self.swe._device_ahead = True
         for ts in self.tracers.values():
             ts._device_ahead = True
+        self._bed_moved()
+
+    def _bed_moved(self):
+        """after a step with solve_exner the host copy of fields.bathymetry_2d is stale (read back on demand, solver2d.py)"""
+        if self.options.sediment_model_options.solve_exner:
+            host = any(getattr(ts, 'host_sediment', False) for ts in self.tracers.values())
+            self.solver._bed_device_ahead = not host            # (the host fallback wrote fields.bathymetry_2d itself)
+            for ts in self.tracers.values():
+                if getattr(ts, 'sediment_model', None) is not None:
+                    ts.sediment_model._planes = None
 
     def diagnostics(self):
         return self.swe.diagnostics()

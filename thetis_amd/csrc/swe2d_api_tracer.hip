@@ -42,6 +42,8 @@ int launch_tracer_stage(Handle *h, int id, int in, int out, double a0, double a1
     Handle::Tracer &t = h->tracers[id];
     // a reacting tracer: its source planes from the current tracer values first (swe2d_reaction.hip)
     if (t.rx.n_code > 0) { if (int rc = reaction_launch(h, id, in, c0, c1)) return rc; }
+    // the sediment field: erosion and deposition from the frozen coefficient planes and the stage's input (swe2d_sediment.hip)
+    if (h->sed.on && id == h->sed.tracer) { if (int rc = sediment_source_launch(h, in, c0, c1)) return rc; }
     SweTracerArgs a;
     fill_tracer_args(h, id, a, in, out, a0, a1, beta, c0, c1, mean_out);
     // triangles: cell integral and interior facets of the diffusion inside the stage kernel, boundary facets by a launch
@@ -351,6 +353,10 @@ int swe2d_tracer_set_source(swe2d_handle *hh, int id, const double *nodal)
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     Handle::Tracer &t = h->tracers[id];
+    if (h->sed.on && id == h->sed.tracer) {
+        if (!nodal) return SWE2D_OK;                     // (no uploaded source: what the sediment field has)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tracer_set_source: the sediment field's source comes from the sediment model (swe2d_sediment_clear first)");
+    }
     t.rx.n_code = 0;                                    // (an uploaded source replaces a reaction program)
     if (!nodal) {
         if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }
@@ -591,7 +597,13 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
         // that covers the handle (cfg 4 on 1 M triangles), stage launches otherwise
         if (!tracer_only) { if (int rc = step_swe(h, kWholeStep, 1)) return rc; }
         else if (forced(h)) h->clock_k_first++;                          // (the forcings' clock counts the steps of this call either way)
-        for (int id = 0; id < (int)h->tracers.size(); id++) {
+        // the reference's order (coupled_timeintegrator_2d.py:100-135): every other tracer, then the sediment model on the new flow -
+        // its coefficients frozen over the step -, the sediment stages, the limiter, the Exner update
+        const int n_tr = (int)h->tracers.size(), sed = h->sed.on ? h->sed.tracer : -1;
+        for (int j = 0; j < n_tr + (sed >= 0 ? 1 : 0); j++) {
+            const int id = j == n_tr ? sed : j;
+            if (j < n_tr && id == sed) continue;
+            if (id == sed) { if (int rc = sediment_update_launch(h)) return rc; }
             // without a diffusion pass behind it the last stage kernel also writes the cell means the limiter starts from
             const bool fuse_mean = use_limiter && !h->tracers[id].diff;
             if (fuse_mean && h->lim_nv == 0) {
@@ -603,6 +615,7 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
                 if (rc) return rc;
             }
             if (use_limiter) { int rc = limiter_apply(h, id, h->n_cells, fuse_mean); if (rc) return rc; }
+            if (id == sed && h->sed.par.solve_exner) { if (int rc = exner_launch(h)) return rc; }
         }
     }
     return SWE2D_OK;

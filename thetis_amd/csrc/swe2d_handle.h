@@ -238,6 +238,19 @@ struct Handle {
     };
     std::vector<Tracer> tracers;
     double *rx_field[SWE2D_REACTION_MAX_FIELDS] = {nullptr, nullptr, nullptr, nullptr};   // coefficient fields of the reaction programs, npc planes
+    // suspended sediment + Exner (swe2d_sediment.hip): on = tracer `tracer` is the sediment field, its source comes from `planes`
+    struct Sediment {
+        bool on = false;
+        int tracer = -1;
+        swe2d_sediment_params par{};
+        double *planes = nullptr;                       // E | D | equilibrium, 3 nodal planes each (swe2d_sediment_update)
+        unsigned eq_markers = 0u;                       // bit m: marker slot m carries 'equilibrium'
+        int *v_off = nullptr, *v_ent = nullptr;         // vertex -> (cell << 2 | local node), cells ascending (the Exner gather)
+        double *area = nullptr;                         // [n_cells]
+        double *vh_new = nullptr;                       // [n_vertices] the Exner kernel's output, copied over vh
+        unsigned *count = nullptr;                      // vertices an Exner update left unchanged (depth below the floor)
+    };
+    Sediment sed;
     int tracer_use_lf = 0;
     double tracer_lf_factor = 1.0, tracer_vel_factor = 1.0;
     std::vector<int> host_cells;                 // [n][3] vertex ids as given (limiter default topology)
@@ -473,6 +486,11 @@ void particles_free_all(Handle *h);
 // ---- reacting tracers (swe2d_reaction.hip)
 int reaction_launch(Handle *h, int id, int in, int c0, int c1);   // in front of a stage launch of tracer `id` reading buffer `in`: its source planes on [c0, c1)
 void reaction_free_all(Handle *h);                      // frees the coefficient fields (swe2d_destroy)
+// ---- suspended sediment + Exner (swe2d_sediment.hip)
+int sediment_source_launch(Handle *h, int in, int c0, int c1);   // in front of a stage launch of the sediment tracer reading buffer `in`
+int sediment_update_launch(Handle *h);                  // E, D, equilibrium from buffer A + the 'equilibrium' facets of the value table
+int exner_launch(Handle *h);                            // one bed update from the sediment tracer's buffer A
+void sediment_free(Handle *h);                          // (swe2d_destroy)
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -196,6 +196,8 @@ int swe2d_tracer_set_reaction(swe2d_handle *hh, int id, int32_t n_code, const in
     if (int rc = reaction_check(h, id)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     Handle::Tracer &t = h->tracers[id];
+    if (h->sed.on && id == h->sed.tracer)
+        return n_code == 0 ? SWE2D_OK : fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tracer_set_reaction: the sediment field's source comes from the sediment model (swe2d_sediment_clear first)");
     if (n_code == 0) {                                                      // no program, no source
         t.rx.n_code = 0;
         if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }

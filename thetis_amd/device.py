@@ -1005,6 +1005,65 @@ class Swe2dDevice(object):
         self._ck(self.lib.swe2d_tracer_diagnostics(self.h, tid, _ptr(out)))
         return out
 
+    # -- suspended sediment + Exner (thetis_amd/sediment_model.py, csrc/swe2d_sediment.hip)
+    def sediment_set(self, tid, params):
+        """tracer ``tid`` becomes the sediment field; ``params``: the fields of ``_lib.SedimentParams`` as a dict
+        (sediment_model.device_parameters)"""
+        p = _lib.SedimentParams()
+        for name, ctype in _lib.SedimentParams._fields_:
+            setattr(p, name, (int if ctype is ctypes.c_int32 else float)(params[name]))
+        self._ck(self.lib.swe2d_sediment_set(self.h, int(tid), ctypes.byref(p)))
+
+    def sediment_set_equilibrium_bc(self, marker, on=True):
+        self._ck(self.lib.swe2d_sediment_set_equilibrium_bc(self.h, self._slot(marker), int(bool(on))))
+
+    def sediment_update(self):
+        """erosion flux, deposition coefficient and equilibrium concentration from the current flow and bed; 'equilibrium' facets"""
+        self._ck(self.lib.swe2d_sediment_update(self.h))
+
+    def sediment_read(self):
+        """(E, D, equilibrium), each (N, 3) nodal"""
+        out = [np.empty((self.n_cells, self.npc)) for _ in range(3)]
+        self._ck(self.lib.swe2d_sediment_read(self.h, *[_ptr(a) for a in out]))
+        return tuple(self._nodal_out(a) for a in out)
+
+    def sediment_read_bc(self):
+        """the sediment tracer's per-facet value table as (N, facet, node)"""
+        a = np.empty((3, self.n_cells, 3))
+        self._ck(self.lib.swe2d_sediment_read_bc(self.h, _ptr(a)))
+        return self._nodal_out(np.ascontiguousarray(a.transpose(1, 0, 2)))
+
+    def sediment_clear(self):
+        self._ck(self.lib.swe2d_sediment_clear(self.h))
+
+    def exner_step(self):
+        self._ck(self.lib.swe2d_exner_step(self.h))
+
+    def exner_skipped(self):
+        n = ctypes.c_int64(0)
+        self._ck(self.lib.swe2d_exner_skipped(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def get_bathymetry(self):
+        """the bathymetry at the vertices (caller's numbering) as the kernels read it: moved by the Exner updates"""
+        b = np.empty(self._keep[1].shape[0])
+        self._ck(self.lib.swe2d_get_bathymetry(self.h, _ptr(b)))
+        if self._vperm is None:
+            return b
+        out = np.empty_like(b)
+        out[self._vperm] = b
+        return out
+
+    def set_bathymetry(self, vertex_values):
+        """replaces the bathymetry at the vertices (caller's numbering)"""
+        b = np.asarray(vertex_values, dtype=np.float64).reshape(-1)
+        if self._vperm is not None:
+            b = b[self._vperm]
+        b = np.ascontiguousarray(b)
+        if b.shape[0] != self._keep[1].shape[0]:
+            raise ValueError('bathymetry must have one value per vertex')
+        self._ck(self.lib.swe2d_set_bathymetry(self.h, _ptr(b)))
+
     def advance_coupled(self, n_steps=1, tracer_only=False, use_limiter=True):
         self._ck(self.lib.swe2d_advance_coupled(self.h, int(n_steps), int(bool(tracer_only)), int(bool(use_limiter))))
 

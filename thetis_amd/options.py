@@ -12,7 +12,7 @@ from collections import OrderedDict
 
 __all__ = ['ModelOptions2d', 'ExplicitSWETimeStepperOptions2d', 'ExplicitTracerTimeStepperOptions2d',
            'TimeStepperOptions', 'Constant', 'TidalTurbineOptions', 'ConstantTidalTurbineOptions',
-           'TabulatedTidalTurbineOptions', 'TidalTurbineFarmOptions', 'DiscreteTidalTurbineFarmOptions']
+           'TabulatedTidalTurbineOptions', 'TidalTurbineFarmOptions', 'DiscreteTidalTurbineFarmOptions', 'SedimentModelOptions']
 
 
 class Constant(object):
@@ -330,6 +330,68 @@ class DiscreteTidalTurbineFarmOptions(TidalTurbineFarmOptions):
     ])
 
 
+_SEDIMENT_STEPPERS = OrderedDict([
+    ('SSPRK33', ExplicitTracerTimeStepperOptions2d), ('ForwardEuler', ExplicitTracerTimeStepperOptions2d),
+    ('BackwardEuler', _ImplicitPlaceholderOptions), ('CrankNicolson', _ImplicitPlaceholderOptions),
+    ('DIRK22', _ImplicitPlaceholderOptions), ('DIRK33', _ImplicitPlaceholderOptions)])
+
+
+def _sediment_model_class():
+    from .sediment_model import SedimentModel
+    return SedimentModel
+
+
+class SedimentModelOptions(FrozenOptions):
+    """Options of the sediment model (options.py:736-835): every trait under the reference's name with its default.  This build
+    runs the suspended load with the explicit steppers; what it refuses is refused when the equations are built."""
+    name = 'Sediment model options'
+    _spec = OrderedDict([
+        ('solve_exner', (False, _bool)),
+        ('solve_suspended_sediment', (False, _bool)),
+        ('use_sediment_conservative_form', (False, _bool)),
+        ('use_bedload', (False, _bool)),
+        ('use_sediment_slide', (False, _bool)),
+        ('horizontal_diffusivity', (None, _scalar_expr_or_none)),
+        ('use_angle_correction', (True, _bool)),
+        ('use_slope_mag_correction', (True, _bool)),
+        ('use_secondary_current', (False, _bool)),
+        ('average_sediment_size', (None, _scalar_expr_or_none)),
+        ('slide_region', (None, _scalar_expr_or_none)),
+        ('bed_reference_height', (None, _scalar_expr_or_none)),
+        ('use_advective_velocity_correction', (True, _bool)),
+        ('porosity', (lambda: Constant(0.4), _scalar_expr_or_none)),
+        ('max_angle', (lambda: Constant(32), _constant)),
+        ('sed_slide_length_scale', (lambda: Constant(0), _constant)),
+        ('morphological_acceleration_factor', (lambda: Constant(1), _constant)),
+        ('morphological_viscosity', (None, _scalar_expr_or_none)),
+        ('sediment_density', (lambda: Constant(2650), _scalar_expr_or_none)),
+        ('secondary_current_parameter', (lambda: Constant(0.75), _constant)),
+        ('slope_effect_parameter', (lambda: Constant(1.3), _constant)),
+        ('slope_effect_angle_parameter', (lambda: Constant(2/3), _constant)),
+        ('check_sediment_conservation', (False, _bool)),
+        ('check_sediment_overshoot', (False, _bool)),
+        ('sediment_model_class', (_sediment_model_class, _any)),
+        # paired enums last so that their slaves exist after construction
+        ('sediment_timestepper_type', ('CrankNicolson', _enum(*_SEDIMENT_STEPPERS))),
+        ('exner_timestepper_type', ('CrankNicolson', _enum(*_SEDIMENT_STEPPERS))),
+    ])
+    _paired = {
+        'sediment_timestepper_type': ('sediment_timestepper_options', _SEDIMENT_STEPPERS),
+        'exner_timestepper_type': ('exner_timestepper_options', _SEDIMENT_STEPPERS),
+    }
+
+    def __init__(self):
+        object.__setattr__(self, 'sediment_timestepper_options', None)
+        object.__setattr__(self, 'exner_timestepper_options', None)
+        super().__init__()
+
+
+def _sediment_options(name, v):
+    if not isinstance(v, SedimentModelOptions):
+        raise TypeError("The '{:}' trait expected a SedimentModelOptions instance, not {!r}".format(name, v))
+    return v
+
+
 class CommonModelOptions(FrozenOptions):
     """Options that are common for both 2d and 3d models (options.py:583-733), hot-path subset + API names."""
     name = 'Model options'
@@ -399,6 +461,7 @@ class ModelOptions2d(CommonModelOptions):
         # subdomain id (``Mesh2d.cell_markers``) or 'everywhere' -> [farm options, ...] (options.py:1004-1011, solver2d.py:462-483)
         ('tidal_turbine_farms', (dict, _any)),
         ('discrete_tidal_turbine_farms', (dict, _any)),
+        ('sediment_model_options', (SedimentModelOptions, _sediment_options)),
         # paired enums last so that their slaves exist after construction
         ('swe_timestepper_type', ('CrankNicolson', _enum(*_SWE_STEPPERS))),
         ('tracer_timestepper_type', ('CrankNicolson', _enum(*_TRACER_STEPPERS))),
@@ -439,6 +502,13 @@ class ModelOptions2d(CommonModelOptions):
         """Set the same timestepper type for all components (options.py:1017-1041)."""
         self.swe_timestepper_type = timestepper_type
         self.tracer_timestepper_type = timestepper_type
+        options = (self.swe_timestepper_options, self.tracer_timestepper_options)
+        if self.sediment_model_options.solve_suspended_sediment:
+            self.sediment_model_options.sediment_timestepper_type = timestepper_type
+            options += (self.sediment_model_options.sediment_timestepper_options,)
+        if self.sediment_model_options.solve_exner:
+            self.sediment_model_options.exner_timestepper_type = timestepper_type
+            options += (self.sediment_model_options.exner_timestepper_options,)
         for key, value in kwargs.items():
-            for option in (self.swe_timestepper_options, self.tracer_timestepper_options):
+            for option in options:
                 setattr(option, key, value)

@@ -64,6 +64,8 @@ class FlowSolver2d(object):
         self.export_initial_state = True
         self.bnd_functions = {'shallow_water': {}, 'tracer': {}, 'sediment': {}}
         self.solve_tracer = False
+        self.sediment_model = None
+        self._bed_device_ahead = False
         self.keep_log = keep_log
         # one process per GPU (python -m torch.distributed.run --nproc-per-node N script.py, the counterpart of the reference's
         # mpiexec -n N): the communicator of this run; COLLECTIVE when WORLD_SIZE > 1 (thetis_amd/comm.py)
@@ -184,6 +186,8 @@ class FlowSolver2d(object):
         self.fields.elev_2d = elev_2d
         for label, topts in self.options.tracer.items():
             self.fields[label] = topts.function if topts.function is not None else Function(self.function_spaces.Q_2d, name=label)
+        if self.options.sediment_model_options.solve_suspended_sediment:
+            self.fields.sediment_2d = Function(self.function_spaces.Q_2d, name='sediment_2d')
         # mesh element size: CG-P1 L2 projection of sqrt(cell area), utility.py:620-640 (needed for automatic dt only)
         self.fields.h_elem_size_2d = None
         self.set_wetting_and_drying_alpha()
@@ -206,6 +210,21 @@ class FlowSolver2d(object):
         self.equations.sw = ShallowWaterEquations(self.function_spaces.H_2d, self.depth, self.options,
                                                   tidal_farms=self.tidal_farms)
         self.equations.sw.bnd_functions = self.bnd_functions['shallow_water']
+        so = self.options.sediment_model_options
+        if so.solve_suspended_sediment or so.solve_exner:
+            # suspended load + Exner on the device: the model refuses by name what this build does not run
+            from .sediment_model import SedimentEquation2D
+            velocity, elevation = self.fields.solution_2d.subfunctions
+            self.sediment_model = so.sediment_model_class(self.options, self.mesh2d, velocity, elevation, self.depth,
+                                                          comm=self.comm, tidal_farms=bool(self.tidal_farms))
+            if so.solve_exner:
+                b = self.fields.bathymetry_2d
+                if not isinstance(b, Function) or b.function_space().family != 'CG':
+                    raise NotImplementedError('sediment_model_options.solve_exner needs bathymetry_2d as a CG-P1 Function (the bed '
+                                              'is evolved at the vertices)')
+                b._pull_hook = self._pull_bathymetry
+            self.equations.sediment = SedimentEquation2D(self.function_spaces.Q_2d, self.depth, self.options, self.sediment_model,
+                                                         conservative=so.use_sediment_conservative_form)
         self.solve_tracer = len(self.options.tracer) > 0
         for label in self.options.tracer:
             self.equations[label] = TracerEquation2D(label, self.function_spaces.Q_2d, self.depth, self.options)
@@ -213,6 +232,26 @@ class FlowSolver2d(object):
             self.tracer_limiter = VertexBasedP1DGLimiter(self.function_spaces.Q_2d, device_id=self.device_id)
         else:
             self.tracer_limiter = None
+
+    def _pull_bathymetry(self):
+        """fields.bathymetry_2d from the device after steps with solve_exner (exports, checkpoints, ``dat.data_ro``)"""
+        if self._bed_device_ahead:
+            self._bed_device_ahead = False
+            b = self.fields.bathymetry_2d
+            b._data[...] = self.timestepper.device.get_bathymetry().reshape(b._data.shape)
+
+    def get_sediment_timestepper(self, integrator, swe_stepper):
+        """the sediment field's stepper (solver2d.py:600-623): one more device tracer, stepped after the user's tracers"""
+        o, so = self.options, self.options.sediment_model_options
+        velocity, elevation = self.fields.solution_2d.subfunctions
+        fields = {'uv_2d': velocity, 'elev_2d': elevation, 'diffusivity_h-sediment_2d': so.horizontal_diffusivity,
+                  'source-sediment_2d': None,
+                  'lax_friedrichs_tracer_scaling_factor': o.lax_friedrichs_tracer_scaling_factor,
+                  'tracer_advective_velocity_factor': o.tracer_advective_velocity_factor}
+        ts = integrator(self.equations.sediment, self.fields.sediment_2d, fields, self.dt, so.sediment_timestepper_options,
+                        self.bnd_functions['sediment'], swe_stepper)
+        ts.attach_sediment(self.sediment_model)
+        return ts
 
     def get_swe_timestepper(self, integrator):
         """Gets shallow water timestepper object with appropriate parameters (solver2d.py:542-573)"""
@@ -278,14 +317,17 @@ class FlowSolver2d(object):
         tracer_steppers = {'SSPRK33': coupled_timeintegrator_2d.DeviceTracerSSPRK33,
                            'ForwardEuler': coupled_timeintegrator_2d.DeviceTracerForwardEuler}
         name = self.options.swe_timestepper_type
-        if self.options.tracer_only and self.options.tracer:
+        if self.options.tracer_only and (self.options.tracer or self.sediment_model is not None):
             name = 'SSPRK33'        # the shallow water state is frozen (coupled_timeintegrator_2d.py:98): the stepper
             #                         object only holds the device-resident velocity, its type option is not used
         if name not in steppers:
             raise NotImplementedError("swe_timestepper_type {!r} needs a global (non)linear solve and is outside the "
                                       "explicit device path; use 'SSPRK33' or 'ForwardEuler'".format(name))
-        if self.solve_tracer:
-            if self.options.tracer_timestepper_type not in tracer_steppers:
+        sediment_steppers = {'SSPRK33': coupled_timeintegrator_2d.DeviceSedimentSSPRK33,
+                             'ForwardEuler': coupled_timeintegrator_2d.DeviceSedimentForwardEuler}
+        solve_sediment = self.sediment_model is not None
+        if self.solve_tracer or solve_sediment:
+            if self.solve_tracer and self.options.tracer_timestepper_type not in tracer_steppers:
                 raise NotImplementedError("tracer_timestepper_type {!r} is outside the explicit device path; use "
                                           "'SSPRK33' or 'ForwardEuler'".format(self.options.tracer_timestepper_type))
             if self.comm.size > 1 and not self.options.tracer_only and self.options.tracer_timestepper_type != name:
@@ -295,6 +337,9 @@ class FlowSolver2d(object):
             tracers = {}
             for system in self.options.tracer_fields:
                 tracers[system] = self.get_tracer_timestepper(tracer_steppers[self.options.tracer_timestepper_type], system, swe)
+            if solve_sediment:                  # last: stepped after the user's tracers
+                so = self.options.sediment_model_options
+                tracers['sediment_2d'] = self.get_sediment_timestepper(sediment_steppers[so.sediment_timestepper_type], swe)
             self.timestepper = coupled_timeintegrator_2d.GeneralCoupledTimeIntegrator2D(self, swe, tracers)
         else:
             self.timestepper = self.get_swe_timestepper(steppers[name])
@@ -319,6 +364,9 @@ class FlowSolver2d(object):
         meta = dict(exporter.field_metadata)
         for label, topts in self.options.tracer.items():
             meta[label] = topts.metadata
+        # thetis/field_defs.py
+        meta['bathymetry_2d'] = {'name': 'Bathymetry', 'shortname': 'Bathymetry', 'unit': 'm', 'filename': 'bathymetry2d'}
+        meta['sediment_2d'] = {'name': 'Sediment', 'shortname': 'Sediment', 'unit': '', 'filename': 'Sediment2d'}
         return meta
 
     def create_exporters(self):
@@ -353,14 +401,25 @@ class FlowSolver2d(object):
         for target, expression in ((elevation, elev), (velocity, uv)):
             if expression is not None:
                 target.project(expression)
+        sediment = tracers.pop('sediment', tracers.pop('sediment_2d', None))
         for name, expression in tracers.items():
             # keyword 'salt' and keyword 'salt_2d' both name the tracer field salt_2d (solver2d.py:773-776)
             label = name if name.endswith('_2d') and len(name) > 3 else name + '_2d'
             if label not in self.options.tracer:
                 raise AssertionError('Unknown tracer label {:}'.format(label))
             self.fields[label].project(expression)
-        # (sediment: out of scope, options.py raises where it is selected)
         self.timestepper.initialize(self.fields.solution_2d)
+        if self.sediment_model is not None:
+            # the model on the initial flow; without an initial field the sediment starts in equilibrium (solver2d.py:772-783)
+            self.timestepper.tracers['sediment_2d'].sediment_update()
+            if sediment is not None:
+                self.fields.sediment_2d.project(sediment)
+            else:
+                eq = self.sediment_model.get_equilibrium_tracer()
+                if self.sediment_model.conservative:
+                    eq = eq*self.sediment_model.host.depth(elevation.cell_node_values(), self.sediment_model._bathymetry())
+                f = self.fields.sediment_2d
+                f.assign(np.asarray(eq).reshape(f._data.shape))
 
     def add_callback(self, callback, eval_interval='export'):
         """solver2d.py:788-797"""
@@ -429,6 +488,11 @@ class FlowSolver2d(object):
             print_output(header)
         line = ' '.join(['{:{fmt}}'.format(e[1], fmt=e[2]) for e in entries])
         print_output(line)
+        if self.sediment_model is not None and self.options.sediment_model_options.solve_exner:
+            n_kept = (self.timestepper.device.exner_skipped() if self.sediment_model.on_device
+                      else self.sediment_model.host.n_skipped)
+            if n_kept:
+                print_output('exner: {:d} vertex updates skipped (depth below the floor)'.format(n_kept))
         sys.stdout.flush()
 
     def iterate(self, update_forcings=None, export_func=None):
@@ -536,5 +600,13 @@ class FlowSolver2d(object):
                 checks.append(make(label, self))
             if o.check_tracer_overshoot:
                 checks.append(callback.TracerOvershootCallBack(label, self))
+        so = o.sediment_model_options
+        if self.sediment_model is not None:
+            if so.check_sediment_conservation:
+                make = (callback.ConservativeTracerMassConservation2DCallback if so.use_sediment_conservative_form
+                        else callback.TracerMassConservation2DCallback)
+                checks.append(make('sediment_2d', self))
+            if so.check_sediment_overshoot:
+                checks.append(callback.TracerOvershootCallBack('sediment_2d', self))
         for c in checks:
             self.add_callback(c, eval_interval='export')

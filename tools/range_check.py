@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 
-def exercise():
+def exercise(only=None):
     from helpers import channel_case, delaunay_case, quad_case
     from thetis_amd import _lib, ordering
     from thetis_amd.device import Swe2dDevice
@@ -27,7 +27,9 @@ def exercise():
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
         for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'atm', 'stats',
-                        'stats+wetting-drying', 'particles', 'particles+wetting-drying', 'reactions'):
+                        'stats+wetting-drying', 'particles', 'particles+wetting-drying', 'reactions', 'sediment'):
+            if only and variant not in only:
+                continue
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
             bath_v = bath - 0.6*bath.max() if variant.endswith('wetting-drying') and not variant.startswith('farms') else (bath + 20.0 if variant.startswith('farms') or variant == 'dfarm' else bath)
             dev = Swe2dDevice(mesh, bath_v, 0.05, boundary_len=mesh.boundary_len)
@@ -253,6 +255,48 @@ def exercise():
                         dev.advance_coupled(2, tracer_only=False, use_limiter=True)
                         assert all(np.isfinite(dev.tracer_get_state(t)).all() for t in range(2)), (name, variant, j)
                         n_launch += 2*(3 + 6 + 1 + 6)*2
+            if variant == 'sediment':
+                # suspended sediment + Exner (csrc/swe2d_sediment.hip): the coefficient kernel reads the state planes, the cell
+                # vertices and the bathymetry and writes the E / D / equilibrium planes; the facet kernel writes the tracer's per-facet
+                # value table over the boundary-cell list; the source kernel runs in front of every stage launch (whole mesh, ragged
+                # sub-ranges, ForwardEuler); the Exner kernel gathers over the vertex -> (cell, node) list, reads the cell areas and
+                # writes the second bathymetry array.  Both forms, a plain tracer next to the field, the batch.  Quadrilaterals: refused.
+                from thetis_amd.sediment_model import device_parameters, sediment_constants
+                cs = sediment_constants(160e-6, 0.025, 1e-6, morfac=50.0)
+                plain = dev.add_tracer()
+                tid = dev.add_tracer()
+                if k == 4:
+                    try:
+                        dev.sediment_set(tid, device_parameters(cs, False, True))
+                        raise AssertionError('the sediment model on quadrilaterals')
+                    except _lib.Swe2dError as e:
+                        assert e.code == _lib.ERR_UNSUPPORTED
+                else:
+                    third = mesh.num_cells//3 + 1
+                    for conservative in (False, True):
+                        dev.sediment_set(tid, device_parameters(cs, conservative, True))
+                        dev.sediment_set_equilibrium_bc(markers[0])
+                        dev.tracer_set_diffusivity(tid, 0.5)
+                        dev.tracer_set_diffusion_bc(tid, markers[0], 4, 0.0)
+                        dev.sediment_update()
+                        E, D, eq = dev.sediment_read()
+                        assert np.isfinite(E).all() and np.isfinite(D).all() and (D > 0).all(), (name, variant)
+                        dev.tracer_set_state(tid, eq*(20.0 if conservative else 1.0))
+                        dev.tracer_set_state(plain, np.ones((mesh.num_cells, k)))
+                        for i in range(3):
+                            dev.tracer_solve_stage(tid, i)
+                        for i in range(3):
+                            dev.tracer_solve_stage_cells(tid, i, 0, third)
+                            dev.tracer_solve_stage_cells(tid, i, third, mesh.num_cells)
+                        dev.tracer_forward_euler(tid)
+                        dev.tracer_limit(tid)
+                        dev.exner_step()
+                        dev.advance_coupled(2, tracer_only=False, use_limiter=True)
+                        assert np.isfinite(dev.tracer_get_state(tid)).all() and np.isfinite(dev.get_bathymetry()).all(), (name, variant)
+                        assert np.isfinite(dev.sediment_read_bc()).all() and np.isfinite(dev.tracer_get_source(tid)).all()
+                        dev.exner_skipped()
+                        dev.sediment_clear()
+                        n_launch += 2 + 3*2 + 6*2 + 2 + 3 + 1 + 2*(3 + 6 + 2 + 6 + 3 + 1)
             dev.advance(2)
             dev.advance_forward_euler(1)
             for i in range(3):                      # sub-range launches with ragged ends
@@ -286,6 +330,8 @@ def exercise():
             dev.close()
             n_launch += 30
             print('ok', name, variant, flush=True)
+    if only:
+        return n_launch
     # partitions: halo cells, owned / interior sub-ranges, pack / unpack
     from thetis_amd.partition import build_partition, rcb_owner
     mesh, bath, uv, eta = channel_case(nx=23, ny=11, seed=4)
@@ -325,9 +371,11 @@ def exercise():
 def main():
     from thetis_amd import _lib
     selftest = os.environ.get('THETIS_AMD_RANGE_SELFTEST') == '1'
+    # python tools/range_check.py [variant,variant,...]: only these variants (and no partitions)
+    only = set(sys.argv[1].split(',')) if len(sys.argv) > 1 else None
     n_launch = 0
     try:
-        n_launch = exercise()
+        n_launch = exercise(only)
     except Exception as e:                       # the negative control suppresses accesses: non-finite states are expected there
         if not selftest:
             raise
