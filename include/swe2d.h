@@ -840,6 +840,45 @@ int  swe2d_get_bathymetry(swe2d_handle *h, double *vertex_values);
 /* synchronises; replaces the bathymetry [n_vertices] (every kernel reads it at launch).  SWE2D_ERR_UNSUPPORTED with wetting-drying */
 int  swe2d_set_bathymetry(swe2d_handle *h, const double *vertex_values);
 
+/* ---- Section transports (csrc/swe2d_sections.hip; thetis_amd/sections.py): volume and tracer flux through lines ----
+ * The reference has no 2D counterpart (its TransectCallback is 3D, thetis/callback.py:959).  A section is a list of PIECES; a piece
+ * is a straight segment inside one cell (a cut of a polyline, or a boundary facet), handed in with its geometry resolved by the host:
+ * the cell, the nodal weights w[q][i] of the cell's nodes at the two Gauss-Legendre points q of the piece, and N = (nx, ny) len/2,
+ * n the unit normal the transport is counted along.  With L = sqrt(Nx Nx + Ny Ny) (= len/2, formed by the host part of the
+ * library) a piece contributes, without contraction and with f_q = fma(w[q][k-1], f[k-1], ... fma(w[q][1], f[1], w[q][0] f[0])) for
+ * f = u, v, eta, h, c_t:
+ *     H_q = eta_q + h_q   (use_nonlinear_equations = 0: h_q)        F_q = H_q fma(u_q, Nx, v_q Ny)
+ *     transport  F_0 + F_1          area  L (H_0 + H_1)          tracer t  fma(F_1, c_t1, F_0 c_t0)
+ * h is the handle's current vertex bathymetry.  On triangles every factor is linear along a piece, so the two points integrate
+ * int H u.n ds, int H ds, int H u.n c ds exactly; the same holds for a piece along an edge of a quadrilateral.  The terms of a
+ * section are added as limb sums (swe2d_diagnostics_limbs): exact and independent of the order of the pieces.
+ * A VALUE ROW is [SWE2D_MAX_SECTIONS][2 + SWE2D_MAX_SECTION_TRACERS]: transport, area, tracer 0 ..; a LIMB ROW has
+ * SWE2D_SECTION_LIMBS int64 per value.  Slots without pieces and tracers not named are 0.  Terms that cannot be summed (not finite,
+ * |x| >= 2^78) are left out and COUNTED per row; the count is handed out, it is not an error of the call.
+ * SWE2D_ERR_UNSUPPORTED: a handle with wetting-drying; any of these calls inside a stream capture.  SWE2D_ERR_INVALID_ARGUMENT: a
+ * cell outside 0 .. n_owned-1, a weight or normal that is not finite, a section slot or tracer id out of range, too many of either,
+ * an append to a full row store.  The handle stays usable after either. */
+#define SWE2D_MAX_SECTIONS 16
+#define SWE2D_MAX_SECTION_TRACERS 4
+#define SWE2D_SECTION_VALUES (2 + SWE2D_MAX_SECTION_TRACERS)
+#define SWE2D_SECTION_LIMBS 6
+/* replaces the handle's sections (synchronises).  piece_section[n_pieces] in 0 .. n_sections-1 (any order; n_sections <=
+ * SWE2D_MAX_SECTIONS), piece_cell[n_pieces], piece_weights[n_pieces][2][nodes_per_cell], piece_normal[n_pieces][2],
+ * tracer_ids[n_tracers] (n_tracers <= SWE2D_MAX_SECTION_TRACERS; may be NULL when 0).  Empties the row store. */
+int  swe2d_sections_set(swe2d_handle *h, int32_t n_sections, int32_t n_pieces, const int32_t *piece_section, const int32_t *piece_cell,
+                        const double *piece_weights, const double *piece_normal, int32_t n_tracers, const int32_t *tracer_ids);
+int  swe2d_sections_clear(swe2d_handle *h);
+/* the state now (buffer A), synchronously: one launch.  limbs [SWE2D_MAX_SECTIONS][SWE2D_SECTION_VALUES][SWE2D_SECTION_LIMBS] /
+ * values [SWE2D_MAX_SECTIONS][SWE2D_SECTION_VALUES] = swe2d_sum_limbs_to_double of them; *n_unsummable: terms left out */
+int  swe2d_sections_eval_limbs(swe2d_handle *h, int64_t *limbs, int64_t *n_unsummable);
+int  swe2d_sections_eval(swe2d_handle *h, double *values, int64_t *n_unsummable);
+/* rows kept on the device: reserve `capacity` rows (empties the store); append enqueues the one launch on the handle's stream (no
+ * synchronisation, no host read); read synchronises, hands out the rows appended since the last read as values[n_rows][..] with
+ * n_unsummable[n_rows] (either may be NULL) and empties the store */
+int  swe2d_sections_rows_reserve(swe2d_handle *h, int32_t capacity);
+int  swe2d_sections_rows_append(swe2d_handle *h);
+int  swe2d_sections_rows_read(swe2d_handle *h, double *values, int64_t *n_unsummable, int32_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ from .expr import *  # noqa: F401,F403  (SpatialCoordinate, conditional, as_vect
 from .forcing import AtmosphericForcing, HarmonicTidalForcing, compute_wind_stress  # noqa: F401
 from .fieldstats import FieldStatisticsCallback  # noqa: F401
 from .particles import ParticleTrackerCallback  # noqa: F401
+from .sections import SectionTransportCallback  # noqa: F401
 from .function import Function, FunctionSpace, get_functionspace  # noqa: F401
 from .mesh import Mesh2d, PeriodicRectangleMesh, RectangleMesh, SquareMesh, UnitSquareMesh  # noqa: F401
 from .meshio import read_gmsh, write_gmsh  # noqa: F401

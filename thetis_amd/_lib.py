@@ -35,6 +35,8 @@ ATM_RHO_AIR = 1.22                    # include/swe2d.h SWE2D_ATM_RHO_AIR
 STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
 PARTICLE_ACTIVE, PARTICLE_EXITED, PARTICLE_LOST = 0, 1, 2   # include/swe2d.h SWE2D_PARTICLE_*: status of a tracked particle
 PARTICLE_MAX_HOPS = 64                # include/swe2d.h SWE2D_PARTICLE_MAX_HOPS: cells one walk may visit
+MAX_SECTIONS, MAX_SECTION_TRACERS = 16, 4   # include/swe2d.h SWE2D_MAX_SECTIONS, SWE2D_MAX_SECTION_TRACERS
+SECTION_VALUES = 2 + MAX_SECTION_TRACERS    # include/swe2d.h SWE2D_SECTION_VALUES: transport, area, one per tracer
 PROBE_UV, PROBE_ELEV = -1, -2  # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
@@ -262,6 +264,13 @@ SYMBOLS = {
     'swe2d_exner_skipped': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
     'swe2d_get_bathymetry': (ctypes.c_int, [_H, _dp]),
     'swe2d_set_bathymetry': (ctypes.c_int, [_H, _dp]),
+    'swe2d_sections_set': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _ip, _ip, _dp, _dp, ctypes.c_int32, _ip]),
+    'swe2d_sections_clear': (ctypes.c_int, [_H]),
+    'swe2d_sections_eval_limbs': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_sections_eval': (ctypes.c_int, [_H, _dp, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_sections_rows_reserve': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_sections_rows_append': (ctypes.c_int, [_H]),
+    'swe2d_sections_rows_read': (ctypes.c_int, [_H, _dp, ctypes.POINTER(ctypes.c_int64), _ip]),
 }
 
 _lib = None

@@ -18,17 +18,21 @@ from .pointeval import PointNotInDomainError, select_and_move_detectors  # noqa:
 __all__ = ['CallbackManager', 'DiagnosticCallback', 'ScalarConservationCallback', 'MinMaxConservationCallback', 'DeviceCheck',
            'VolumeConservation2DCallback', 'TracerMassConservation2DCallback',
            'ConservativeTracerMassConservation2DCallback', 'TracerOvershootCallBack', 'DetectorsCallback', 'TimeSeriesCallback2D',
-           'PointNotInDomainError', 'select_and_move_detectors', 'FieldStatisticsCallback', 'ParticleTrackerCallback']
+           'PointNotInDomainError', 'select_and_move_detectors', 'FieldStatisticsCallback', 'ParticleTrackerCallback',
+           'SectionTransportCallback']
 
 
 def __getattr__(name):
-    # (thetis_amd/fieldstats.py and thetis_amd/particles.py build on DiagnosticCallback below: resolved on first use)
+    # (thetis_amd/fieldstats.py, thetis_amd/particles.py and thetis_amd/sections.py build on DiagnosticCallback below: resolved on first use)
     if name == 'FieldStatisticsCallback':
         from .fieldstats import FieldStatisticsCallback
         return FieldStatisticsCallback
     if name == 'ParticleTrackerCallback':
         from .particles import ParticleTrackerCallback
         return ParticleTrackerCallback
+    if name == 'SectionTransportCallback':
+        from .sections import SectionTransportCallback
+        return SectionTransportCallback
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))
 
 

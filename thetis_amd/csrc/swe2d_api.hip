@@ -547,6 +547,7 @@ void swe2d_destroy(swe2d_handle *hh)
     particles_free_all(h);
     reaction_free_all(h);
     sediment_free(h);
+    sections_free(h);
     for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
     for (auto &t : h->tracers) {

@@ -330,6 +330,18 @@ struct Handle {
         double *out = nullptr;                          // [capacity][n][2] recorded positions
     };
     std::vector<Particles> particles;
+    // section transports (swe2d_sections.hip): n_lanes > 0 = the handle has sections
+    struct Sections {
+        int n_lanes = 0;                                // lanes of a launch: every section's pieces padded to whole workgroups
+        int n_tracers = 0;
+        int tracer_ids[SWE2D_MAX_SECTION_TRACERS] = {0};
+        int block0[SWE2D_MAX_SECTIONS + 1] = {0};       // first workgroup of every section slot (block0[s + 1] - block0[s] = its workgroups)
+        int *cell = nullptr;                            // [n_lanes] device cell, -1: padding
+        double *geom = nullptr;                         // [2*npc + 3][n_lanes]: w[0][.], w[1][.], Nx, Ny, L
+        unsigned long long *rows = nullptr;             // [rows_cap + 1][SWE_SECTION_ROW] limb sums; the last row is swe2d_sections_eval's
+        int rows_cap = 0, rows_n = 0;
+    };
+    Sections sections;
     swe2d_params par{};
     SweBcTable bc{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -491,6 +503,8 @@ int sediment_source_launch(Handle *h, int in, int c0, int c1);   // in front of 
 int sediment_update_launch(Handle *h);                  // E, D, equilibrium from buffer A + the 'equilibrium' facets of the value table
 int exner_launch(Handle *h);                            // one bed update from the sediment tracer's buffer A
 void sediment_free(Handle *h);                          // (swe2d_destroy)
+// ---- section transports (swe2d_sections.hip): frees the piece tables and the rows (swe2d_destroy)
+void sections_free(Handle *h);
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -1064,6 +1064,62 @@ class Swe2dDevice(object):
             raise ValueError('bathymetry must have one value per vertex')
         self._ck(self.lib.swe2d_set_bathymetry(self.h, _ptr(b)))
 
+    # -- section transports: csrc/swe2d_sections.hip (the pieces come from thetis_amd/sections.py)
+    def sections_set(self, n_sections, piece_section, piece_cell, piece_weights, piece_normal, tracer_ids=()):
+        """the handle's sections: per piece its section slot, cell (caller numbering), weights (2, k) at the two Gauss points and
+        (nx, ny)*len/2; ``tracer_ids``: tracers whose flux is summed too"""
+        cells = np.asarray(piece_cell, dtype=np.int64).reshape(-1)
+        inside = (cells >= 0) & (cells < self.n_cells)
+        dev = cells if self.perm is None else np.where(inside, self.inv_perm[np.where(inside, cells, 0)], -1)
+        dev = np.ascontiguousarray(dev, dtype=np.int32)
+        sec = np.ascontiguousarray(np.asarray(piece_section, dtype=np.int64).reshape(-1), dtype=np.int32)
+        w = np.ascontiguousarray(np.asarray(piece_weights, dtype=np.float64).reshape(len(dev), 2, self.npc))
+        nrm = np.ascontiguousarray(np.asarray(piece_normal, dtype=np.float64).reshape(len(dev), 2))
+        if len(sec) != len(dev):
+            raise ValueError('one section slot per piece')
+        tids = np.ascontiguousarray(list(tracer_ids), dtype=np.int32)
+        self._ck(self.lib.swe2d_sections_set(self.h, int(n_sections), len(dev), _iptr(sec), _iptr(dev), _ptr(w), _ptr(nrm),
+                                             len(tids), _iptr(tids) if len(tids) else None))
+        self._section_rows_cap = 0
+
+    def sections_clear(self):
+        self._ck(self.lib.swe2d_sections_clear(self.h))
+
+    def sections_eval_limbs(self):
+        """(limb sums (MAX_SECTIONS, SECTION_VALUES, SUM_LIMBS) of transport, area, tracer fluxes of the state now; terms left out)"""
+        limbs = np.zeros(_lib.MAX_SECTIONS*_lib.SECTION_VALUES*_lib.SUM_LIMBS, dtype=np.int64)
+        bad = ctypes.c_int64(0)
+        self._ck(self.lib.swe2d_sections_eval_limbs(self.h, limbs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(bad)))
+        return limbs.reshape(_lib.MAX_SECTIONS, _lib.SECTION_VALUES, _lib.SUM_LIMBS), int(bad.value)
+
+    def sections_eval(self):
+        """(values (MAX_SECTIONS, SECTION_VALUES) of the state now, synchronously; terms left out)"""
+        out = np.zeros((_lib.MAX_SECTIONS, _lib.SECTION_VALUES))
+        bad = ctypes.c_int64(0)
+        self._ck(self.lib.swe2d_sections_eval(self.h, _ptr(out), ctypes.byref(bad)))
+        return out, int(bad.value)
+
+    def sections_rows_reserve(self, capacity):
+        self._ck(self.lib.swe2d_sections_rows_reserve(self.h, int(capacity)))
+        self._section_rows_cap = int(capacity)
+
+    def sections_rows_capacity(self):
+        return getattr(self, '_section_rows_cap', 0)
+
+    def sections_rows_append(self):
+        """one row of the current state, enqueued (no synchronisation)"""
+        self._ck(self.lib.swe2d_sections_rows_append(self.h))
+
+    def sections_rows_read(self):
+        """the rows appended since the last read: (values (rows, MAX_SECTIONS, SECTION_VALUES), terms left out (rows,)); the store
+        is empty afterwards"""
+        cap = max(self.sections_rows_capacity(), 1)
+        out = np.empty((cap, _lib.MAX_SECTIONS, _lib.SECTION_VALUES))
+        bad = np.zeros(cap, dtype=np.int64)
+        n = ctypes.c_int32()
+        self._ck(self.lib.swe2d_sections_rows_read(self.h, _ptr(out), bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(n)))
+        return out[:n.value].copy(), bad[:n.value].copy()
+
     def advance_coupled(self, n_steps=1, tracer_only=False, use_limiter=True):
         self._ck(self.lib.swe2d_advance_coupled(self.h, int(n_steps), int(bool(tracer_only)), int(bool(use_limiter))))
 

@@ -27,7 +27,7 @@ def exercise(only=None):
         k = mesh.cells.shape[1]
         cxy = mesh.cell_xy()
         for variant in ('plain', 'open+fields', 'sources', 'viscosity', 'wetting-drying', 'tracers', 'farms', 'farms+wetting-drying', 'dfarm', 'tide', 'atm', 'stats',
-                        'stats+wetting-drying', 'particles', 'particles+wetting-drying', 'reactions', 'sediment'):
+                        'stats+wetting-drying', 'particles', 'particles+wetting-drying', 'reactions', 'sediment', 'sections'):
             if only and variant not in only:
                 continue
             # (farms: deep water, so that the radicand of the upwind correction stays positive)
@@ -297,6 +297,32 @@ def exercise(only=None):
                         dev.exner_skipped()
                         dev.sediment_clear()
                         n_launch += 2 + 3*2 + 6*2 + 2 + 3 + 1 + 2*(3 + 6 + 2 + 6 + 3 + 1)
+            if variant == 'sections':
+                # section transports (csrc/swe2d_sections.hip): swe_section_transport_kernel reads the piece tables (cell, weights,
+                # normals), the state planes, the cell vertices, the bathymetry and the tracers' planes through the checked loads;
+                # the limb sums are atomics on host-checked sizes (capacity + 1 rows).  A polyline of more than one workgroup
+                # (triangles), every boundary marker, an unused slot, a last workgroup with padding lanes; rows between steps.
+                from thetis_amd import sections as sec
+                tids = [dev.add_tracer(), dev.add_tracer()]
+                for t in tids:
+                    dev.tracer_set_state(t, np.ones((mesh.num_cells, k)))
+                lo, hi = cxy.reshape(-1, 2).min(axis=0), cxy.reshape(-1, 2).max(axis=0)
+                parts = [None] + [sec.boundary_pieces(mesh, m) for m in markers]
+                if k == 3:
+                    parts.append(sec.cut_polyline(mesh, [lo + 0.01*(hi - lo), hi - 0.02*(hi - lo), lo + (0.9, 0.05)*(hi - lo)]))
+                live = [(s_, p_) for s_, p_ in enumerate(parts) if p_ is not None]
+                dev.sections_set(len(parts), np.concatenate([np.full(len(p_), s_) for s_, p_ in live]),
+                                 np.concatenate([p_.cell for _, p_ in live]), np.concatenate([p_.weights for _, p_ in live]),
+                                 np.concatenate([p_.normal for _, p_ in live]), tids)
+                dev.sections_rows_reserve(3)
+                for _ in range(3):
+                    dev.advance_coupled(1, tracer_only=False, use_limiter=True)
+                    dev.sections_rows_append()
+                rows, bad = dev.sections_rows_read()
+                values, bad_now = dev.sections_eval()
+                assert len(rows) == 3 and not bad.any() and bad_now == 0 and np.isfinite(rows).all(), (name, variant)
+                assert np.array_equal(rows[2], values) and (values[1:len(parts), 1] > 0).all() and not values[0].any()
+                n_launch += 3*(3 + 6 + 1) + 4
             dev.advance(2)
             dev.advance_forward_euler(1)
             for i in range(3):                      # sub-range launches with ragged ends
