@@ -56,6 +56,15 @@ int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std:
     HIP_TRY(h, hipMalloc(&ts.counts, counts.size()*sizeof(int)));
     HIP_TRY(h, hipMemcpy(ts.tile, rec.data(), rec.size()*sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(ts.counts, counts.data(), counts.size()*sizeof(int), hipMemcpyHostToDevice));
+    // the sources of the staging slots: int2 {first, count} per tile, then the neighbour codes (one spare entry: never an empty allocation)
+    std::vector<int> slots;
+    for (size_t i = 0; i + 1 < t.slot_first.size(); i++) { slots.push_back(t.slot_first[i]); slots.push_back(t.slot_first[i + 1] - t.slot_first[i]); }
+    std::vector<int> src(t.slot_src);
+    src.push_back(0);
+    HIP_TRY(h, hipMalloc(&ts.slots, slots.size()*sizeof(int)));
+    HIP_TRY(h, hipMalloc(&ts.slot_src, src.size()*sizeof(int)));
+    HIP_TRY(h, hipMemcpy(ts.slots, slots.data(), slots.size()*sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(ts.slot_src, src.data(), src.size()*sizeof(int), hipMemcpyHostToDevice));
     ts.n_tiles = (int)t.n_inner.size();
     ts.ring[0] = t.ring[0]; ts.ring[1] = t.ring[1];
     return SWE2D_OK;
@@ -66,6 +75,8 @@ void free_tiles(TileSet &ts)
 {
     if (ts.tile) (void)hipFree(ts.tile);
     if (ts.counts) (void)hipFree(ts.counts);
+    if (ts.slots) (void)hipFree(ts.slots);
+    if (ts.slot_src) (void)hipFree(ts.slot_src);
     ts = TileSet();
 }
 
@@ -138,6 +149,8 @@ int launch_fuse123(Handle *h, int cell_end)
     q.st.idxc = h->opt[SWE2D_OPT_COMPACT_IDX] == 0 ? nullptr : h->idxc;
     q.tile = static_cast<const int2 *>(h->fuse3.tile);
     q.counts = reinterpret_cast<const int2 *>(h->fuse3.counts);
+    q.slots = reinterpret_cast<const int2 *>(h->fuse3.slots);
+    q.slot_src = h->fuse3.slot_src;
     q.n_tiles = h->fuse3.n_tiles;
     q.cell_end = cell_end;
     for (int s = 0; s < 3; s++) { q.a0[s] = s ? kAlpha0[s] : 0.0; q.a1[s] = s ? kAlphaIn[s] : 1.0; q.beta[s] = kBeta[s]; }

@@ -251,8 +251,20 @@ __device__ __forceinline__ bool swe_flow_arrived(swe_u32x4 g, unsigned need)
 //  three-stage kernel of swe2d_fuse.h; SWE_GEOM_KEEP: evaluated here and left in the lane's LDS record, geo[f*PLANE] = Lf and
 //  geo[(3 + f)*PLANE] = 1/Lf of facet f; SWE_GEOM_STORED: taken from the record a SWE_GEOM_KEEP call filled - the values that
 //  instruction sequence gave, so the same bits; SWE_GEOM_* are defined in swe2d_tri.h, whose finish treats 1/twoA in the same way)
+// (TRB, NTR = 1 only: how tr[f][0] holds its two addresses - SWE_TR_INDEX: in doubles, every caller but the three-stage kernel;
+//  SWE_TR_BYTES: in bytes, no shift is left between the word and the DS instruction; SWE_TR_BYTES_INSIDE: in bytes, and the caller
+//  knows that every trace lies in the planes - stages 2 and 3 of the three-stage kernel -, so the components are 3*PLANE and 6*PLANE
+//  doubles on: immediate offsets of the DS instruction, nothing to select and nothing to add)
+#define SWE_TR_INDEX 0
+#define SWE_TR_BYTES 1
+#define SWE_TR_BYTES_INSIDE 2
+#ifdef SWE_RANGE_CHECK
+#define SWE_LDSB(p_, b_, n_) ((p_)[SWE_LDSI((b_) >> 3, n_)])
+#else
+#define SWE_LDSB(p_, b_, n_) (*reinterpret_cast<const double *>(reinterpret_cast<const char *>(p_) + (b_)))
+#endif
 template <bool NONLIN, bool LF, bool SRC, int NTR, bool WD = false, int XG = SWE_FLOW_XG, int PLANE = SWE_BLOCK, int NLDS = SWE_FLOW_LDS_DOUBLES,
-          int GEOM = SWE_GEOM_COMPUTE>
+          int GEOM = SWE_GEOM_COMPUTE, int TRB = SWE_TR_INDEX>
 __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k, const double u[3], const double v[3], const double e[3],
                                                     const double h[3], const double *lds, const unsigned tr[3][NTR], int bmarkers,
                                                     const double nx[3], const double ny[3], double twoA, double bu[3], double bv[3],
@@ -264,12 +276,21 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
         const int a = f, b = (f + 1) % 3;
         // tr[f][c] = address of component c (u, v, e) at the neighbour's node on my node f + 1 | the same on my node f << 16
         const unsigned ab0 = tr[f][0] & 0xffffu, aa0 = tr[f][0] >> 16;
-        const unsigned step = ab0 >= (unsigned)XG ? 1u : (unsigned)(3*PLANE);
-        const unsigned ab1 = NTR == 3 ? tr[f][NTR - 2] & 0xffffu : ab0 + step, aa1 = NTR == 3 ? tr[f][NTR - 2] >> 16 : aa0 + step;
-        const unsigned ab2 = NTR == 3 ? tr[f][NTR - 1] & 0xffffu : ab0 + 2u*step, aa2 = NTR == 3 ? tr[f][NTR - 1] >> 16 : aa0 + 2u*step;
-        const double unb = lds[SWE_LDSI(ab0, NLDS)], una = lds[SWE_LDSI(aa0, NLDS)];
-        const double vnb = lds[SWE_LDSI(ab1, NLDS)], vna = lds[SWE_LDSI(aa1, NLDS)];
-        const double enb = lds[SWE_LDSI(ab2, NLDS)], ena = lds[SWE_LDSI(aa2, NLDS)];
+        double unb, una, vnb, vna, enb, ena;
+        if constexpr (TRB == SWE_TR_INDEX) {
+            const unsigned step = ab0 >= (unsigned)XG ? 1u : (unsigned)(3*PLANE);
+            const unsigned ab1 = NTR == 3 ? tr[f][NTR - 2] & 0xffffu : ab0 + step, aa1 = NTR == 3 ? tr[f][NTR - 2] >> 16 : aa0 + step;
+            const unsigned ab2 = NTR == 3 ? tr[f][NTR - 1] & 0xffffu : ab0 + 2u*step, aa2 = NTR == 3 ? tr[f][NTR - 1] >> 16 : aa0 + 2u*step;
+            unb = lds[SWE_LDSI(ab0, NLDS)]; una = lds[SWE_LDSI(aa0, NLDS)];
+            vnb = lds[SWE_LDSI(ab1, NLDS)]; vna = lds[SWE_LDSI(aa1, NLDS)];
+            enb = lds[SWE_LDSI(ab2, NLDS)]; ena = lds[SWE_LDSI(aa2, NLDS)];
+        } else {
+            static_assert(TRB == SWE_TR_INDEX || NTR == 1, "byte addresses: one packed word per facet");
+            const unsigned step = TRB == SWE_TR_BYTES_INSIDE ? (unsigned)(24*PLANE) : (ab0 >= (unsigned)(8*XG) ? 8u : (unsigned)(24*PLANE));
+            unb = SWE_LDSB(lds, ab0, NLDS); una = SWE_LDSB(lds, aa0, NLDS);
+            vnb = SWE_LDSB(lds, ab0 + step, NLDS); vna = SWE_LDSB(lds, aa0 + step, NLDS);
+            enb = SWE_LDSB(lds, ab0 + 2u*step, NLDS); ena = SWE_LDSB(lds, aa0 + 2u*step, NLDS);
+        }
         double Lf, rLf;
         if constexpr (GEOM == SWE_GEOM_STORED) { Lf = geo[f*PLANE]; rLf = geo[(3 + f)*PLANE]; }
         else swe_tri_facet_len(nx[f], ny[f], Lf, rLf);

@@ -232,6 +232,8 @@ struct SweFuse3Args {
     SweStageArgs st;          // uin = U(0) (state buffer A); geometry, connectivity, boundary tables; dt, g, sigma_lf
     const int2 *tile;         // [n_tiles][256]: as SweFuseArgs::tile (lane of the neighbour in the tile, or bit 9 + staging slot)
     const int2 *counts;       // [n_tiles]: {n_inner, n_mid | rot << 16}: roles 0 .. n_inner-1 interior, .. n_mid-1 ring 1; role r on lane (r + 64 rot) & 255
+    const int2 *slots;        // [n_tiles]: {first entry of the tile in slot_src, number of staging slots}
+    const int *slot_src;      // per staging slot the neighbour code of the facet that reads it: (cell << 2) | the cell's facet (swe2d_tiles.h)
     int n_tiles;
     int cell_end;             // stage 3 (the only one that leaves the chip) on cells [0, cell_end): a partition's last stage range
     double a0[3], a1[3], beta[3];   // Shu-Osher weights per stage (swe2d_ssprk33_coefficients)
@@ -258,10 +260,22 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
 #ifdef SWE_WAVE_TIMING
     int wt_bodies = __any(real) ? 1 : 0;                   // profiling build only (tools/fuse3timing.py): stage bodies this wave executes
 #endif
+    // The traces from outside the tile are gathered by SLOT, not by lane and facet (round 19): only ring 2 has facets towards the outside,
+    // ~84 slots of a bench tile, where a gather per lane and facet issued 18 loads in every lane for the ~500 of 4608 that were read.
+    // Slot s is the work of physical lane 64*(s & 3) + (s >> 2): the slots are dealt round over the four waves, whatever the tile's
+    // rotation - each wave, hence each SIMD, issues the six loads once with a quarter of the slots' lanes active, and the barrier behind
+    // the prologue waits for four equal shares instead of one or two full waves (224 slots at most: 56 lanes of a wave).
+    const int2 sl = q.slots[tile];
+    const int slot = ((lane & 63) << 2) | (lane >> 6);
+    int scode = -1;                                        // the slot's source (cell << 2) | facet, fetched before the cell's own chain of loads starts
+    if (slot < sl.y) scode = q.slot_src[sl.x + slot];
 
     int bmarkers = 0, bkind1 = 0;
+    // per facet the BYTE addresses of component 0's two traces (swe_flow_rhs_facets, SWE_TR_BYTES): 16 bits each
     unsigned tr[3][1];
     double h[3], nx[3], ny[3], u[3], v[3], e[3];
+    double px[3], py[3];
+    const swe_rsrc_t gu = swe_rsrc(p.uin), gv = swe_rsrc(p.uin + 3*S), ge = swe_rsrc(p.uin + 6*S);
     if (real) {
         int nb[3], vid[3];
         swe_conn_load(p.idxc, p.idx4, p.idx2, k, nb, vid);
@@ -270,36 +284,24 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             const int m1 = (bmarkers & 0xff) ? (bmarkers & 0xff) : ((bmarkers & 0xff00) ? ((bmarkers >> 8) & 0xff) : (bmarkers >> 16));
             bkind1 = m1 < SWE_MAX_MARKERS ? p.bc.kind[m1] : 0;
         }
-        const swe_rsrc_t gu = swe_rsrc(p.uin), gv = swe_rsrc(p.uin + 3*S), ge = swe_rsrc(p.uin + 6*S);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             u[i] = swe_ld(gu, k8, i*S8);
             v[i] = swe_ld(gv, k8, i*S8);
             e[i] = swe_ld(ge, k8, i*S8);
         }
-        double r0[3][6];
-        bool outside[3];
 #pragma unroll
         for (int f = 0; f < 3; f++) {
             const int nbf = nb[f];
             const unsigned w = ((unsigned)tl.y >> (SWE_FUSE_FBITS*f)) & 0x3ffu;
-            outside[f] = (w & 0x200u) != 0u;
+            const bool outside = (w & 0x200u) != 0u;
             const unsigned at = w & 0x1ffu;                                   // lane in the tile, or staging slot
+            // the neighbour traverses the shared facet backwards: its node f2 sits on my node f + 1, its node (f2 + 1) % 3 on my node f
             const int f2 = nbf >= 0 ? (nbf & 3) : f, f2a = f2 == 2 ? 0 : f2 + 1;
-            {
-                const unsigned ab = outside[f] ? (unsigned)(SWE_FUSE3_XG + 6*at) : (unsigned)(f2*SWE_FUSE_WG + at);
-                const unsigned aa = outside[f] ? (unsigned)(SWE_FUSE3_XG + 6*at + 3) : (unsigned)(f2a*SWE_FUSE_WG + at);
-                tr[f][0] = ab | (aa << 16);
-            }
-            const int code = outside[f] ? nbf : ((k << 2) | f);
-            const unsigned kn8 = (unsigned)(code >> 2)*8u;
-            const int g2 = code & 3;
-            const unsigned ob = kn8 + (g2 == 0 ? 0u : (g2 == 1 ? S8 : 2u*S8));         // node g2
-            const unsigned oa = kn8 + (g2 == 0 ? S8 : (g2 == 1 ? 2u*S8 : 0u));         // node (g2 + 1) % 3
-            r0[f][0] = swe_ld(gu, ob, 0); r0[f][1] = swe_ld(gv, ob, 0); r0[f][2] = swe_ld(ge, ob, 0);
-            r0[f][3] = swe_ld(gu, oa, 0); r0[f][4] = swe_ld(gv, oa, 0); r0[f][5] = swe_ld(ge, oa, 0);
+            const unsigned ab = outside ? (unsigned)(8*SWE_FUSE3_XG) + 48u*at : (unsigned)(8*SWE_FUSE_WG*f2) + 8u*at;
+            const unsigned aa = outside ? (unsigned)(8*SWE_FUSE3_XG + 24) + 48u*at : (unsigned)(8*SWE_FUSE_WG*f2a) + 8u*at;
+            tr[f][0] = ab | (aa << 16);
         }
-        double px[3], py[3];
         const swe_rsrc_t rvx = swe_rsrc(p.vx), rvy = swe_rsrc(p.vy), rvh = swe_rsrc(p.vh);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -308,6 +310,17 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             py[i] = swe_ld(rvy, v8, 0);
             h[i] = swe_ld(rvh, v8, 0);
         }
+    }
+    double r0[6];
+    if (scode >= 0) {                                      // issued behind the cell's own loads, before anything waits for those
+        const unsigned kn8 = (unsigned)(scode >> 2)*8u;
+        const int g2 = scode & 3;
+        const unsigned ob = kn8 + (g2 == 0 ? 0u : (g2 == 1 ? S8 : 2u*S8));         // node g2: on the reader's node f + 1
+        const unsigned oa = kn8 + (g2 == 0 ? S8 : (g2 == 1 ? 2u*S8 : 0u));         // node (g2 + 1) % 3: on the reader's node f
+        r0[0] = swe_ld(gu, ob, 0); r0[1] = swe_ld(gv, ob, 0); r0[2] = swe_ld(ge, ob, 0);
+        r0[3] = swe_ld(gu, oa, 0); r0[4] = swe_ld(gv, oa, 0); r0[5] = swe_ld(ge, oa, 0);
+    }
+    if (real) {
 #pragma unroll
         for (int f = 0; f < 3; f++) {
             const int b = (f + 1) % 3;
@@ -316,14 +329,10 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         }
 #pragma unroll
         for (int i = 0; i < 3; i++) { lds[i*SWE_FUSE_WG + lane] = u[i]; lds[(3 + i)*SWE_FUSE_WG + lane] = v[i]; lds[(6 + i)*SWE_FUSE_WG + lane] = e[i]; }
+    }
+    if (scode >= 0) {
 #pragma unroll
-        for (int f = 0; f < 3; f++) {
-            if (outside[f]) {
-                const unsigned at = ((unsigned)tl.y >> (SWE_FUSE_FBITS*f)) & 0x1ffu;
-#pragma unroll
-                for (int j = 0; j < 6; j++) lds[SWE_LDSI(SWE_FUSE3_XG + 6*at + j, SWE_FUSE3_LDS)] = r0[f][j];
-            }
-        }
+        for (int j = 0; j < 6; j++) lds[SWE_LDSI(SWE_FUSE3_XG + 6*slot + j, SWE_FUSE3_LDS)] = r0[j];
     }
     __syncthreads();
     // ---- stage 1 on every cell of the tile: U(1) = U(0) + beta1 dt M^-1 R(U(0)), into P1
@@ -336,7 +345,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         double H[3];
         swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
         swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
-        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1, SWE_TR_BYTES>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                      nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
@@ -374,7 +383,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             double H[3];
             swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
             swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
-            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23, SWE_TR_BYTES_INSIDE>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                           nullptr, nullptr, G);
             const double a0 = q.a0[s], a1 = q.a1[s];
 #pragma unroll

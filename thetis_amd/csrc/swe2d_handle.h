@@ -101,6 +101,8 @@ extern std::atomic<unsigned long long> g_next_uid;
 struct TileSet {
     void *tile = nullptr;                               // [n_tiles][256] records: int2, quadrilaterals int4 (SweFuseArgs / SweFuseQuadArgs / SweFuse3Args)
     int *counts = nullptr;                              // [n_tiles] n_inner; two-ring tiles: int2 {n_inner, n_mid | rot << 16}
+    int *slots = nullptr;                               // [n_tiles] int2 {first slot in slot_src, number of staging slots}
+    int *slot_src = nullptr;                            // neighbour code of every staging slot, tile after tile (swe2d_tiles.h)
     int n_tiles = 0;
     long long ring[2] = {0, 0};                         // cells of ring 1 / ring 2 over all tiles
 };

@@ -8,6 +8,9 @@
 // Per role and facet the table holds a 10-bit field: the lane of the neighbour in the tile (a boundary facet: the lane itself) or,
 // with bit 9 set, the staging slot of a neighbour outside the tile - only facets of the outermost ring lead there, slots are counted
 // per tile in role order.  How the fields are packed into device records is the caller's (swe2d_api_fuse.hip).
+// Next to the fields, per tile, the SOURCE of every staging slot: the neighbour code of the facet that names the slot ((neighbour << 2) |
+// the neighbour's facet g: its nodes g and (g + 1) % 3 lie on the shared facet), slot after slot - slot_src[slot_first[tile] + slot],
+// slot_first[n_tiles] = the total.  A kernel that gathers the traces from outside the tile slot by slot needs nothing else.
 //
 // Lanes: role r sits on the physical lane (r + 64*rot) & (wg - 1); rot = 0 unless the spec rotates.  In the three-stage kernel the wave
 // that holds the last 64 roles runs two stage bodies, the other three run three; which wave that is follows from rot, and rot from the
@@ -43,6 +46,8 @@ struct TileTable {
     std::vector<unsigned> facet;           // [n_tiles*wg*nfacets] 10-bit fields, by physical lane
     std::vector<int> n_inner, n_mid, rot;  // [n_tiles]: roles below n_inner are interior, below n_mid ring 1
     long long ring[2] = {0, 0};            // cells of ring 1 / ring 2 over all tiles
+    std::vector<int> slot_src;             // neighbour code of every staging slot, tile after tile
+    std::vector<int> slot_first;           // [n_tiles + 1]: where a tile's slots start in slot_src
 };
 
 // nbr: packed neighbour codes [nfacets][stride], (neighbour << 2) | its facet, or -marker on the boundary.  order: a permutation of
@@ -58,6 +63,7 @@ inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *or
     std::vector<int> lane_of((size_t)n, -1), touched, inner;
     std::vector<std::pair<int, unsigned char>> undo;
     int count[4] = {0, 0, 0, 0};
+    t.slot_first.push_back(0);
     auto set = [&](int c, unsigned char ns) {
         undo.push_back({c, state[c]});
         if (state[c] == 0) touched.push_back(c);
@@ -122,12 +128,14 @@ inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *or
                 else {
                     if (l < outermost || n_out >= sp.max_out) { err = std::string(who) + "ring bookkeeping"; return 1; }
                     field = kTileOutside | (unsigned)n_out++;
+                    t.slot_src.push_back(code);
                 }
                 t.facet[(base + phys(l))*nf + f] = field;
             }
         }
         t.n_inner.push_back(ni); t.n_mid.push_back(nm); t.rot.push_back(rot);
         t.ring[0] += count[2]; t.ring[1] += count[3];
+        t.slot_first.push_back((int)t.slot_src.size());
         for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
     }
     return 0;
