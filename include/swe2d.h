@@ -831,7 +831,9 @@ int  swe2d_sediment_read(swe2d_handle *h, double *erosion, double *deposition, d
 int  swe2d_sediment_read_bc(swe2d_handle *h, double *facet_nodal);
 /* the tracer is a plain tracer without a source again; the tables are freed */
 int  swe2d_sediment_clear(swe2d_handle *h);
-/* one bed update from the sediment tracer's buffer A with the handle's dt (asynchronous) */
+/* one bed update from the sediment tracer's buffer A with the handle's dt (asynchronous).  With a bedload model the contribution
+ * planes of the last swe2d_bedload_update are added; a handle with bedload and no sediment field is updated from them alone, and
+ * swe2d_exner_skipped counts for it too */
 int  swe2d_exner_step(swe2d_handle *h);
 /* synchronises; vertices left unchanged by the bed updates since swe2d_sediment_set */
 int  swe2d_exner_skipped(swe2d_handle *h, int64_t *n_skipped);
@@ -839,6 +841,75 @@ int  swe2d_exner_skipped(swe2d_handle *h, int64_t *n_skipped);
 int  swe2d_get_bathymetry(swe2d_handle *h, double *vertex_values);
 /* synchronises; replaces the bathymetry [n_vertices] (every kernel reads it at launch).  SWE2D_ERR_UNSUPPORTED with wetting-drying */
 int  swe2d_set_bathymetry(swe2d_handle *h, const double *vertex_values);
+
+/* ---- Bedload transport in the Exner update (thetis/sediment_model.py:213-310 get_bedload_term, thetis/exner_eq.py:87-129), in this
+ * build's formulation: nodal closures from the cell's own DG values, lumped CG-P1 Exner, an explicit bed - the reference's "new"
+ * bathymetry in slopecoef, calfamod and the secondary current is the old one, so ForwardEuler and SSPRK33 of the Exner stepper stay the
+ * same single update.  With or without a sediment field (swe2d_sediment_set) on the handle.
+ * Nodal transport q_b = (qbx, qby), per cell k and local node i from the node's (u, v), H = eta + h (linear equations: h) and the
+ * cell-constant gradients of the bed and of the free surface, j over the cell's nodes in order, d psi_j the gradient table below:
+ *   hx = (h_0*dpsi_0x + h_1*dpsi_1x) + h_2*dpsi_2x, hy likewise;  (ex, ey) the same of eta_j (linear equations: 0, as the reference's
+ *   depth_tot.dx - bathymetry.dx vanishes).  Every comparison a select, no contraction, g the handle's g_grav:
+ *   U2, qfc, mu as for the suspended load above (one function in the kernels)
+ *   stress = rho0*0.5*qfc*U2;  thetaprime = mu*stress/shields_den;  moves = thetaprime > thetacr
+ *   x = moves ? thetaprime - thetacr : 0;  phi = moves ? 8*x*sqrt(x) : 0;  sn = moves ? sqrt(U2) : 1;  calfa = u/sn;  salfa = v/sn
+ *   magnitude correction:  slopecoef = 1 + beta*(hx*calfa + hy*salfa)            [off: 1; not clipped, as in the reference]
+ *   angle correction:      cparam = shields_den*(surbeta2*surbeta2);  tt1 = sqrt(cparam/max(stress, 1e-10))
+ *                          aa = salfa + tt1*hy;  bb = calfa + tt1*hx;  nrm = max(sqrt(aa*aa + bb*bb), 1e-10);  (ca, sa) = (bb, aa)/nrm
+ *                                                                                 [off: (ca, sa) = (calfa, salfa)]
+ *   secondary current:     vs = u*ey - v*ex;  tdf = 7*g*rho0*H*qfc/(2*alpha_secc*(moves ? U2 : 1))
+ *                          t1 = stress*slopecoef*ca + v*tdf*vs;  t2 = stress*slopecoef*sa - u*tdf*vs;  t4 = sqrt(t1*t1 + t2*t2)
+ *                          factor = t4/(moves ? stress : 1);  (ca, sa) = (t1, t2)/(t4 > 0 ? t4 : 1)     [off: factor = slopecoef]
+ *   q_b = (factor*phi*qb_scale)*(ca, sa)  where phi > 0 (and, with the secondary current, t4 > 0);  (0, 0) exactly elsewhere -
+ *   water at rest included, where the reference's u/sqrt(U2) is 0/0.  Products and quotients associate from the left.
+ * Divergence: q_b is the P1 interpolant of its nodal values in the cell.  The contribution of cell k to its node i is
+ *   c_i = -(A*(mx*dpsi_ix + my*dpsi_iy)),  mx = ((qbx_0 + qbx_1) + qbx_2)/3, my likewise, and then, for the facets f = 0, 1, 2 of the
+ *   cell in order (facet f joins the nodes a = f and b = (f+1)%3, o = (f+2)%3 opposite) that lie on an OPEN marker, with
+ *   N = (-((2*A)*dpsi_ox), -((2*A)*dpsi_oy)) = length * outward normal:
+ *     c_a = c_a + ((2*qbx_a + qbx_b)*Nx + (2*qby_a + qby_b)*Ny)/6;   c_b = c_b + ((2*qbx_b + qbx_a)*Nx + (2*qby_b + qby_a)*Ny)/6
+ *   Interior facets contribute nothing (the test space is continuous); a closed boundary facet contributes nothing (no transport through it).
+ *   Gradient table, built by the host part of the library without contraction, det = (x1-x0)*(y2-y0) - (x2-x0)*(y1-y0):
+ *     dpsi_0 = ((y1-y2)/det, (x2-x1)/det);  dpsi_1 = ((y2-y0)/det, (x0-x2)/det);  dpsi_2 = ((y0-y1)/det, (x1-x0)/det)
+ * Exner with bedload: the gather adds nb = sum of c_{k,i} over the vertex's list, separately, and  b_v = b_v + ((dt*fac)*(num + nb))/den
+ *   (exner_eq.py:127-129: bathymetry positive downwards, a positive divergence of q_b deepens the bed); without a sediment field num = 0.
+ *   A handle without bedload executes (dt*fac)*num/den as before.  With the magnitude correction the update is diffusive in h and explicit:
+ *   dt*fac is bounded by the caller.
+ * Per time step (swe2d_advance_coupled, and swe2d_advance for a handle with bedload and solve_exner): flow, tracers, sediment stages,
+ * limiter, swe2d_bedload_update, Exner.  The dataflow kernel declines a handle whose bed moves.  Every other entry that steps the flow
+ * (swe2d_advance_forward_euler, swe2d_solve_stage and its variants, swe2d_solve_flow, swe2d_advance_timed per launch) steps the flow
+ * alone and leaves the bed where it is: a caller of those issues swe2d_bedload_update and swe2d_exner_step itself. */
+typedef struct swe2d_bedload_params {
+    double beta;             /* slope_effect_parameter (magnitude correction) */
+    double surbeta2;         /* slope_effect_angle_parameter */
+    double alpha_secc;       /* secondary_current_parameter */
+    double thetacr;          /* critical Shields parameter */
+    double shields_den;      /* (rhos - rho0)*g*d50 */
+    double qb_scale;         /* sqrt(g*R*d50^3) */
+    double ks;               /* as swe2d_sediment_params: bed_reference_height */
+    double ksp;              /* 3*d50 */
+    double kappa;
+    double rho0;
+    double fac;              /* morphological_acceleration_factor/(1 - porosity): read by the Exner update of a handle without a sediment field */
+    double min_depth;        /* likewise: floor of the depth in the Exner update, > 0 */
+    int32_t use_slope_mag_correction;
+    int32_t use_angle_correction;
+    int32_t use_secondary_current;
+    int32_t solve_exner;     /* swe2d_advance_coupled / swe2d_advance update the bed after every step */
+    uint32_t open_markers;   /* bit m: boundary facets of marker slot m are open to the transport */
+    int32_t fuse_with_sediment; /* 1: with a sediment field whose ks, ksp and kappa are these, swe2d_sediment_update writes q_b and the
+                              * contributions in the coefficient pass's launch (friction closures once per node for both), and
+                              * swe2d_advance_coupled has no bedload launch of its own - the same bits; 0 (the measured choice, DESIGN.md
+                              * 5h): a launch of its own after the limiter */
+} swe2d_bedload_params;
+/* switches the bedload model on or replaces its parameters (allocates the q_b and contribution planes, the gradient table and, where
+ * the handle has none yet, the Exner tables).  SWE2D_ERR_UNSUPPORTED: the cases of swe2d_sediment_set. */
+int  swe2d_bedload_set(swe2d_handle *h, const swe2d_bedload_params *par);
+/* q_b and the contribution planes from buffer A and the current bed (asynchronous) */
+int  swe2d_bedload_update(swe2d_handle *h);
+/* synchronises; the planes as nodal [n_cells][3]; any pointer may be NULL */
+int  swe2d_bedload_read(swe2d_handle *h, double *qbx, double *qby, double *contrib);
+/* no bedload in the Exner update any more; the planes are freed (and the Exner tables of a handle without a sediment field) */
+int  swe2d_bedload_clear(swe2d_handle *h);
 
 /* ---- Section transports (csrc/swe2d_sections.hip; thetis_amd/sections.py): volume and tracer flux through lines ----
  * The reference has no 2D counterpart (its TransectCallback is 3D, thetis/callback.py:959).  A section is a list of PIECES; a piece

@@ -111,6 +111,15 @@ class SedimentParams(ctypes.Structure):
                 ('conservative', ctypes.c_int32), ('solve_exner', ctypes.c_int32)]
 
 
+class BedloadParams(ctypes.Structure):
+    """include/swe2d.h swe2d_bedload_params"""
+    _fields_ = [('beta', ctypes.c_double), ('surbeta2', ctypes.c_double), ('alpha_secc', ctypes.c_double), ('thetacr', ctypes.c_double),
+                ('shields_den', ctypes.c_double), ('qb_scale', ctypes.c_double), ('ks', ctypes.c_double), ('ksp', ctypes.c_double),
+                ('kappa', ctypes.c_double), ('rho0', ctypes.c_double), ('fac', ctypes.c_double), ('min_depth', ctypes.c_double),
+                ('use_slope_mag_correction', ctypes.c_int32), ('use_angle_correction', ctypes.c_int32),
+                ('use_secondary_current', ctypes.c_int32), ('solve_exner', ctypes.c_int32), ('open_markers', ctypes.c_uint32), ('fuse_with_sediment', ctypes.c_int32)]
+
+
 # every symbol include/swe2d.h declares: name -> (restype, argtypes)
 _H = ctypes.c_void_p
 SYMBOLS = {
@@ -262,6 +271,10 @@ SYMBOLS = {
     'swe2d_sediment_clear': (ctypes.c_int, [_H]),
     'swe2d_exner_step': (ctypes.c_int, [_H]),
     'swe2d_exner_skipped': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_bedload_set': (ctypes.c_int, [_H, ctypes.POINTER(BedloadParams)]),
+    'swe2d_bedload_update': (ctypes.c_int, [_H]),
+    'swe2d_bedload_read': (ctypes.c_int, [_H, _dp, _dp, _dp]),
+    'swe2d_bedload_clear': (ctypes.c_int, [_H]),
     'swe2d_get_bathymetry': (ctypes.c_int, [_H, _dp]),
     'swe2d_set_bathymetry': (ctypes.c_int, [_H, _dp]),
     'swe2d_sections_set': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _ip, _ip, _dp, _dp, ctypes.c_int32, _ip]),

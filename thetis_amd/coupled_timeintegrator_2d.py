@@ -322,14 +322,15 @@ class _SedimentStepper(object):
         self.device.tracer_set_source(self.tid, m.host.source(E, D, self.device.tracer_get_buffer(self.tid, i_in), eta, bath))
 
     def exner_step(self, solver):
-        """the bed update after the sediment step (and limiter)"""
+        """the bed update after the sediment step (and limiter), the bedload pass on the new flow in front of it"""
+        m = self.sediment_model
+        contrib = m.update_bedload() if m.use_bedload else None
         if not self.host_sediment:
             self.device.exner_step()
             return
-        m = self.sediment_model
         E, D, _ = m._terms()
         eta, bath = self._host_fields()
-        new = m.host.exner(E, D, self.device.tracer_get_state(self.tid), eta, bath, self.dt)
+        new = m.host.exner(E, D, self.device.tracer_get_state(self.tid), eta, bath, self.dt, bedload=contrib)
         self.device.set_bathymetry(new)
         b = solver.fields.bathymetry_2d
         b._data[...] = new.reshape(b._data.shape)
@@ -362,8 +363,39 @@ class DeviceSedimentForwardEuler(_SedimentStepper, DeviceTracerForwardEuler):
     pass
 
 
+class BedloadStepper(object):
+    """The bed of a run with ``use_bedload`` and no sediment field (the reference's meander): after the flow step (and the tracers)
+    the bedload pass and the Exner update, on the device where it has the calls, through ``HostSediment`` and ``set_bathymetry``
+    otherwise."""
+
+    def __init__(self, model, device, dt):
+        self.sediment_model, self.device, self.dt = model, device, dt
+        self.host_sediment = not hasattr(device, 'bedload_set')
+        if not self.host_sediment:
+            model.bind_bedload_device(device)
+        elif not hasattr(device, 'set_bathymetry'):
+            raise NotImplementedError('sediment_model_options: a device class without the bedload pass must give set_bathymetry for '
+                                      'the host evaluation')
+
+    def set_dt(self, dt):
+        self.dt = dt
+
+    def exner_step(self, solver):
+        m = self.sediment_model
+        contrib = m.update_bedload()
+        if not self.host_sediment:
+            self.device.exner_step()
+            return
+        new = m.host.exner(None, None, None, m.elev.cell_node_values(), m._bathymetry(), self.dt, bedload=contrib)
+        self.device.set_bathymetry(new)
+        b = solver.fields.bathymetry_2d
+        b._data[...] = new.reshape(b._data.shape)
+        b._host_version += 1
+
+
 class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
-    def __init__(self, solver, swe_stepper, tracer_steppers):
+    def __init__(self, solver, swe_stepper, tracer_steppers, bed=None):
+        self.bed = bed                          # a BedloadStepper: the bed of a run without a sediment field
         self.solver = solver
         self.options = solver.options
         self.fields = solver.fields
@@ -385,10 +417,13 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         self.host_reactions = any(ts._host_reaction is not None for ts in self.reacting)
         # (a sediment field the HOST evaluates needs the stage buffers as well: stage by stage)
         self.host_reactions = self.host_reactions or any(getattr(ts, 'host_sediment', False) for ts in tracer_steppers.values())
+        self.host_reactions = self.host_reactions or (bed is not None and bed.host_sediment)
 
     def set_dt(self, dt):
         for stepper in sorted(self.timesteppers):
             self.timesteppers[stepper].set_dt(dt)
+        if self.bed is not None:
+            self.bed.set_dt(dt)
 
     def initialize(self, solution2d):
         assert solution2d == self.fields.solution_2d
@@ -436,6 +471,9 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             if sed is not None and self.options.sediment_model_options.solve_exner:
                 ts.exner_step(self.solver)
                 self._bed_moved()
+        if self.bed is not None:                # no sediment field: the bedload pass on the new flow, then the bed
+            self.bed.exner_step(self.solver)
+            self._bed_moved()
 
     @property
     def forced_per_stage(self):
@@ -482,10 +520,14 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
         """after a step with solve_exner the host copy of fields.bathymetry_2d is stale (read back on demand, solver2d.py)"""
         if self.options.sediment_model_options.solve_exner:
             host = any(getattr(ts, 'host_sediment', False) for ts in self.tracers.values())
+            host = host or (self.bed is not None and self.bed.host_sediment)
+            if self.bed is not None:
+                self.bed.sediment_model._qb = None
             self.solver._bed_device_ahead = not host            # (the host fallback wrote fields.bathymetry_2d itself)
             for ts in self.tracers.values():
                 if getattr(ts, 'sediment_model', None) is not None:
                     ts.sediment_model._planes = None
+                    ts.sediment_model._qb = None
 
     def diagnostics(self):
         return self.swe.diagnostics()

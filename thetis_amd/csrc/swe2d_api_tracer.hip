@@ -615,7 +615,14 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
                 if (rc) return rc;
             }
             if (use_limiter) { int rc = limiter_apply(h, id, h->n_cells, fuse_mean); if (rc) return rc; }
-            if (id == sed && h->sed.par.solve_exner) { if (int rc = exner_launch(h)) return rc; }
+            // (fused: this step's sediment update wrote q_b already, from the flow and the bed that are still there)
+            if (id == sed && h->bed.on && !bedload_fused(h)) { if (int rc = bedload_update_launch(h)) return rc; }
+            if (id == sed && exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
+        }
+        // bedload without a sediment field: the pass on the new flow, then the bed
+        if (sed < 0 && h->bed.on) {
+            if (int rc = bedload_update_launch(h)) return rc;
+            if (exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
         }
     }
     return SWE2D_OK;

@@ -253,6 +253,14 @@ struct Handle {
         unsigned *count = nullptr;                      // vertices an Exner update left unchanged (depth below the floor)
     };
     Sediment sed;
+    // bedload transport in the Exner update (swe2d_sediment.hip); shares the Exner tables of `sed`, with or without a sediment field
+    struct Bedload {
+        bool on = false;
+        swe2d_bedload_params par{};
+        double *planes = nullptr;                       // qbx [3][S] | qby [3][S] | contribution [3][S] (swe2d_bedload_update)
+        double *grad = nullptr;                         // d psi_i/dx [3][S] | d psi_i/dy [3][S], built on the host
+    };
+    Bedload bed;
     int tracer_use_lf = 0;
     double tracer_lf_factor = 1.0, tracer_vel_factor = 1.0;
     std::vector<int> host_cells;                 // [n][3] vertex ids as given (limiter default topology)
@@ -503,7 +511,13 @@ void reaction_free_all(Handle *h);                      // frees the coefficient
 // ---- suspended sediment + Exner (swe2d_sediment.hip)
 int sediment_source_launch(Handle *h, int in, int c0, int c1);   // in front of a stage launch of the sediment tracer reading buffer `in`
 int sediment_update_launch(Handle *h);                  // E, D, equilibrium from buffer A + the 'equilibrium' facets of the value table
-int exner_launch(Handle *h);                            // one bed update from the sediment tracer's buffer A
+int exner_launch(Handle *h);                            // one bed update from the sediment tracer's buffer A and / or the bedload planes
+int bedload_update_launch(Handle *h);                   // q_b and its contribution planes from buffer A and the current bed
+bool bedload_fused(const Handle *h);                    // sediment_update_launch writes them too (one launch for both closures)
+inline bool exner_steps(const Handle *h)                // the bed moves after every step of swe2d_advance_coupled / swe2d_advance
+{
+    return (h->sed.on && h->sed.par.solve_exner) || (h->bed.on && h->bed.par.solve_exner);
+}
 void sediment_free(Handle *h);                          // (swe2d_destroy)
 // ---- section transports (swe2d_sections.hip): frees the piece tables and the rows (swe2d_destroy)
 void sections_free(Handle *h);

@@ -14,7 +14,13 @@
 //                               ascending cell order of  A/12 (2 r_i + r_j + r_k)  and  A/3,  r = E - D*S the net erosion at the nodes.
 //                               The new bed goes to a second array and is copied over the old one afterwards: in the conservative form r
 //                               reads the depth, i.e. the bed of OTHER vertices.  No atomics but the counter of vertices left unchanged.
-// The last three are + - * / in a fixed order without contraction: thetis_amd/sediment_model.py (HostSediment) gives their bits from the
+// swe_bedload_kernel         - with a bedload model (swe2d_bedload_set), once per time step after the flow, sediment and limiter passes, one
+//                               lane per cell: Meyer-Peter-Mueller transport q_b at the cell's three nodes with the slope and secondary
+//                               current corrections (include/swe2d.h has the formulas), from the cell's nodal uv and H and the cell-constant
+//                               gradients of the bed and of the free surface; then the cell's three contributions to the divergence of q_b
+//                               tested with the vertex hat functions, boundary integral of the open facets included.  Written: six q_b
+//                               planes and three contribution planes, which the Exner gather adds up per vertex in list order.
+// The last three and the contribution planes are + - * / in a fixed order without contraction: thetis_amd/sediment_model.py (HostSediment) gives their bits from the
 // same planes.  All loads and stores of a lane are its own cell's / vertex's; plane accesses are coalesced, the gather is not.
 #include "swe2d_handle.h"
 
@@ -28,6 +34,7 @@ struct SweSedArgs {
     const int *list;                            // boundary cells | CSR offsets
     const int *ent;                             // CSR entries: cell << 2 | local node
     const double *area;                         // [n_cells]
+    const double *contrib;                      // Exner with bedload: the contribution planes [3][S]
     unsigned *count;
     size_t stride;
     int begin, end;                             // cell range / list length / vertices
@@ -37,21 +44,41 @@ struct SweSedArgs {
     swe2d_sediment_params par;
 };
 
+// squared speed, friction coefficient and skin friction ratio at one node: shared by the suspended load and the bedload closures
+__device__ __forceinline__ void swe_sediment_friction(double ks, double ksp, double kappa, double u, double v, double H,
+                                                      double &unorm, double &qfc, double &mu)
+{
+#pragma clang fp contract(off)
+    unorm = u*u + v*v;
+    const double hc = H > 0.001 ? H : 0.001;
+    const double ax = 11.036*hc/ks;
+    const double aux = ax > 1.001 ? ax : 1.001;
+    const double lq = log(aux)/kappa;
+    qfc = 2.0/(lq*lq);
+    const bool deep = H > ksp;
+    const double lc = (1.0/kappa)*log(11.036*(deep ? H : ksp)/ksp);
+    const double cfactor = deep ? 2.0/(lc*lc) : 0.0;
+    mu = qfc > 0.0 ? cfactor/qfc : 0.0;
+}
+
+__device__ __forceinline__ void swe_sediment_erosion(const swe2d_sediment_params &p, double unorm, double qfc, double mu, double H,
+                                                     double &E, double &D, double &ceq);
+
 // the closures at one node (include/swe2d.h, swe2d_sediment_params); no argument of log / pow / sqrt leaves its domain on any branch
 __device__ __forceinline__ void swe_sediment_closures(const swe2d_sediment_params &p, double u, double v, double H,
                                                       double &E, double &D, double &ceq)
 {
 #pragma clang fp contract(off)
-    const double unorm = u*u + v*v;
-    const double hc = H > 0.001 ? H : 0.001;
-    const double ax = 11.036*hc/p.ks;
-    const double aux = ax > 1.001 ? ax : 1.001;
-    const double lq = log(aux)/p.kappa;
-    const double qfc = 2.0/(lq*lq);
-    const bool deep = H > p.ksp;
-    const double lc = (1.0/p.kappa)*log(11.036*(deep ? H : p.ksp)/p.ksp);
-    const double cfactor = deep ? 2.0/(lc*lc) : 0.0;
-    const double mu = qfc > 0.0 ? cfactor/qfc : 0.0;
+    double unorm, qfc, mu;
+    swe_sediment_friction(p.ks, p.ksp, p.kappa, u, v, H, unorm, qfc, mu);
+    swe_sediment_erosion(p, unorm, qfc, mu, H, E, D, ceq);
+}
+
+// ... and what follows the friction: Rouse profile, erosion flux, deposition coefficient
+__device__ __forceinline__ void swe_sediment_erosion(const swe2d_sediment_params &p, double unorm, double qfc, double mu, double H,
+                                                     double &E, double &D, double &ceq)
+{
+#pragma clang fp contract(off)
     const double B = p.a > H ? 1.0 : p.a/H;
     const double ustar = sqrt(0.5*qfc*unorm);
     const double rouse = p.ws/(p.kappa*ustar) - 1.0;                       // (still water: +inf, the minimum below takes 3)
@@ -138,6 +165,133 @@ __global__ void __launch_bounds__(256) swe_sediment_source_kernel(SweSedArgs a)
     }
 }
 
+struct SweBedArgs {
+    const double *state;                        // buffer A
+    const int *cv, *nbr;
+    const double *vh;
+    const double *grad;                         // d psi/dx [3][S] | d psi/dy [3][S]
+    const double *area;
+    double *planes;                             // qbx [3][S] | qby [3][S] | contribution [3][S]
+    double *sed_planes;                         // COEF: E [3][S] | D [3][S] | equilibrium [3][S] of the sediment field
+    size_t stride;
+    int n_cells, nonlinear;
+    double g;
+    swe2d_bedload_params par;
+    swe2d_sediment_params sed;                  // COEF
+};
+
+// q_b at one node (include/swe2d.h, swe2d_bedload_params).  `moves` implies U2 > 0, stress > 0 and mu > 0, and every divisor that can
+// vanish elsewhere is replaced by 1 there: no division, root or logarithm sees an argument outside its domain on any branch.
+template <bool MAG, bool ANG, bool SEC>
+__device__ __forceinline__ void swe_bedload_transport(const swe2d_bedload_params &p, double g, double u, double v, double H, double unorm,
+                                                      double qfc, double mu, double hx, double hy, double ex, double ey, double &qx, double &qy)
+{
+#pragma clang fp contract(off)
+    const double stress = p.rho0*0.5*qfc*unorm;
+    const double thetaprime = mu*stress/p.shields_den;
+    const bool moves = thetaprime > p.thetacr;
+    const double x = moves ? thetaprime - p.thetacr : 0.0;
+    const double phi = moves ? 8.0*x*sqrt(x) : 0.0;
+    const double sn = moves ? sqrt(unorm) : 1.0;
+    const double calfa = u/sn, salfa = v/sn;
+    const double slopecoef = MAG ? 1.0 + p.beta*(hx*calfa + hy*salfa) : 1.0;
+    double ca = calfa, sa = salfa;
+    if (ANG) {
+        const double cparam = p.shields_den*(p.surbeta2*p.surbeta2);
+        const double tt1 = sqrt(cparam/(stress > 1e-10 ? stress : 1e-10));
+        const double aa = salfa + tt1*hy, bb = calfa + tt1*hx;
+        const double comb = sqrt(aa*aa + bb*bb);
+        const double nrm = comb > 1e-10 ? comb : 1e-10;
+        ca = bb/nrm;
+        sa = aa/nrm;
+    }
+    double factor = slopecoef;
+    bool live = phi > 0.0;
+    if (SEC) {
+        const double vs = u*ey - v*ex;
+        const double tdf = 7.0*g*p.rho0*H*qfc/(2.0*p.alpha_secc*(moves ? unorm : 1.0));
+        const double t1 = stress*slopecoef*ca + v*tdf*vs;
+        const double t2 = stress*slopecoef*sa - u*tdf*vs;
+        const double t4 = sqrt(t1*t1 + t2*t2);
+        const double t4s = t4 > 0.0 ? t4 : 1.0;
+        factor = t4/(moves ? stress : 1.0);
+        ca = t1/t4s;
+        sa = t2/t4s;
+        live = live && t4 > 0.0;
+    }
+    const double qtot = factor*phi*p.qb_scale;
+    qx = live ? qtot*ca : 0.0;
+    qy = live ? qtot*sa : 0.0;
+}
+
+// COEF: the launch is the sediment field's coefficient pass as well (E, D, equilibrium as swe_sediment_coeff_kernel writes them), the
+// friction closures evaluated once per node for both; the host takes it only where both models hold the same ks, ksp and kappa
+template <bool MAG, bool ANG, bool SEC, bool COEF>
+__global__ void __launch_bounds__(256) swe_bedload_kernel(SweBedArgs a)
+{
+#pragma clang fp contract(off)
+    const int k = blockIdx.x*256 + threadIdx.x;
+    if (k >= a.n_cells) return;
+    const size_t S = a.stride;
+    const unsigned k8 = (unsigned)k*8u, k4 = (unsigned)k*4u, S8 = (unsigned)S*8u, S4 = (unsigned)S*4u;
+    const swe_rsrc_t ru = swe_rsrc(a.state), rv = swe_rsrc(a.state + 3*S), re = swe_rsrc(a.state + 6*S), rc = swe_rsrc(a.cv),
+                     rh = swe_rsrc(a.vh), rn = swe_rsrc(a.nbr), rgx = swe_rsrc(a.grad), rgy = swe_rsrc(a.grad + 3*S), ra = swe_rsrc(a.area);
+    const swe_rsrc_t ox = swe_rsrc(a.planes), oy = swe_rsrc(a.planes + 3*S), oc = swe_rsrc(a.planes + 6*S);
+    double u[3], v[3], eta[3], h[3], gx[3], gy[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        u[i] = swe_ld(ru, k8, i*S8);
+        v[i] = swe_ld(rv, k8, i*S8);
+        eta[i] = swe_ld(re, k8, i*S8);
+        h[i] = swe_ld(rh, (unsigned)swe_ldi(rc, k4, i*S4)*8u, 0u);
+        gx[i] = swe_ld(rgx, k8, i*S8);
+        gy[i] = swe_ld(rgy, k8, i*S8);
+    }
+    const double A = swe_ld(ra, k8, 0u);
+    const double hx = (h[0]*gx[0] + h[1]*gx[1]) + h[2]*gx[2], hy = (h[0]*gy[0] + h[1]*gy[1]) + h[2]*gy[2];
+    const double ex = a.nonlinear ? (eta[0]*gx[0] + eta[1]*gx[1]) + eta[2]*gx[2] : 0.0;
+    const double ey = a.nonlinear ? (eta[0]*gy[0] + eta[1]*gy[1]) + eta[2]*gy[2] : 0.0;
+    double qx[3], qy[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double H = a.nonlinear ? eta[i] + h[i] : h[i];
+        double unorm, qfc, mu;
+        swe_sediment_friction(a.par.ks, a.par.ksp, a.par.kappa, u[i], v[i], H, unorm, qfc, mu);
+        if (COEF) {
+            double E, D, ceq;
+            swe_sediment_erosion(a.sed, unorm, qfc, mu, H, E, D, ceq);
+            swe_st(swe_rsrc(a.sed_planes), k8, i*S8, E);
+            swe_st(swe_rsrc(a.sed_planes + 3*S), k8, i*S8, D);
+            swe_st(swe_rsrc(a.sed_planes + 6*S), k8, i*S8, ceq);
+        }
+        swe_bedload_transport<MAG, ANG, SEC>(a.par, a.g, u[i], v[i], H, unorm, qfc, mu, hx, hy, ex, ey, qx[i], qy[i]);
+    }
+    const double mx = ((qx[0] + qx[1]) + qx[2])/3.0, my = ((qy[0] + qy[1]) + qy[2])/3.0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) c[i] = -(A*(mx*gx[i] + my*gy[i]));
+#pragma unroll
+    for (int f = 0; f < 3; f++) {
+        const int code = swe_ldi(rn, k4, f*S4);
+        const unsigned slot = 0u - (unsigned)code;
+        const bool open = code < 0 && slot < 32u && ((a.par.open_markers >> (slot & 31u)) & 1u);
+        const int b = (f + 1) % 3, o = (f + 2) % 3;
+        const double Nx = -((2.0*A)*gx[o]), Ny = -((2.0*A)*gy[o]);
+        const double ta = ((2.0*qx[f] + qx[b])*Nx + (2.0*qy[f] + qy[b])*Ny)/6.0;
+        const double tb = ((2.0*qx[b] + qx[f])*Nx + (2.0*qy[b] + qy[f])*Ny)/6.0;
+        c[f] = open ? c[f] + ta : c[f];
+        c[b] = open ? c[b] + tb : c[b];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        swe_st(ox, k8, i*S8, qx[i]);
+        swe_st(oy, k8, i*S8, qy[i]);
+        swe_st(oc, k8, i*S8, c[i]);
+    }
+}
+
+// SED: the net erosion of the sediment field; BED: the bedload contribution planes (a.contrib).  <true, false> is the update of a handle
+// without bedload, operation by operation what it was before there was one.
+template <bool SED, bool BED>
 __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
 {
 #pragma clang fp contract(off)
@@ -145,18 +299,19 @@ __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
     if (v >= a.end) return;
     const size_t S = a.stride;
     const unsigned S8 = (unsigned)S*8u, S4 = (unsigned)S*4u;
+    const swe_rsrc_t rb = swe_rsrc(a.contrib);
     const swe_rsrc_t rE = swe_rsrc(a.planes), rD = swe_rsrc(a.planes + 3*S), re = swe_rsrc(a.state + 6*S), rc = swe_rsrc(a.cv),
                      rh = swe_rsrc(a.vh), rt = swe_rsrc(a.tin), rl = swe_rsrc(a.list), rn = swe_rsrc(a.ent), ra = swe_rsrc(a.area);
     const int e0 = swe_ldi(rl, (unsigned)v*4u, 0u), e1 = swe_ldi(rl, (unsigned)v*4u, 4u);
     const double b_old = swe_ld(rh, (unsigned)v*8u, 0u);
-    double num = 0.0, den = 0.0, eta_min = 1e300;
+    double num = 0.0, nb = 0.0, den = 0.0, eta_min = 1e300;
     for (int e = e0; e < e1; e++) {
         const int ent = swe_ldi(rn, (unsigned)e*4u, 0u);
         const int k = ent >> 2, i = ent & 3;
         const unsigned k8 = (unsigned)k*8u, k4 = (unsigned)k*4u;
-        double r[3];
+        double r[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < 3; j++) {
+        for (int j = 0; SED && j < 3; j++) {
             const double E = swe_ld(rE, k8, j*S8), D = swe_ld(rD, k8, j*S8), c = swe_ld(rt, k8, j*S8);
             if (a.conservative) {
                 const double h = swe_ld(rh, (unsigned)swe_ldi(rc, k4, j*S4)*8u, 0u);
@@ -170,14 +325,15 @@ __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
         const double rj = i == 0 ? r[1] : (i == 1 ? r[2] : r[0]);
         const double rk = i == 0 ? r[2] : (i == 1 ? r[0] : r[1]);
         const double A = swe_ld(ra, k8, 0u);
-        num = num + (A/12.0)*((2.0*ri + rj) + rk);
+        if (SED) num = num + (A/12.0)*((2.0*ri + rj) + rk);
+        if (BED) nb = nb + swe_ld(rb, k8, (unsigned)i*S8);
         den = den + A/3.0;
         const double eta = swe_ld(re, k8, (unsigned)i*S8);
         eta_min = eta < eta_min ? eta : eta_min;
     }
     double b_new = b_old;
     if (e1 > e0) {
-        const double b = b_old + (a.dtf*num)/den;
+        const double b = BED ? b_old + (a.dtf*(num + nb))/den : b_old + (a.dtf*num)/den;
         // the shallowest depth the DG elevation gives at this vertex on the new bed (linear equations: the bed itself)
         const double Hmin = a.nonlinear ? eta_min + b : b;
         if (Hmin >= a.min_depth) b_new = b;
@@ -187,6 +343,8 @@ __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
 }
 
 namespace {
+
+int bedload_launch(Handle *h, bool with_coefficients);
 
 int sediment_check(Handle *h, const char *who)
 {
@@ -217,9 +375,14 @@ void sediment_release_tables(Handle *h)
 void sediment_release(Handle *h)
 {
     Handle::Sediment &s = h->sed;
-    void *ptrs[] = {s.planes, s.v_off, s.v_ent, s.area, s.vh_new, s.count};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    s = Handle::Sediment();
+    if (s.planes) (void)hipFree(s.planes);
+    Handle::Sediment none;
+    if (h->bed.on) {                                    // the bedload model goes on reading the Exner tables
+        none.v_off = s.v_off; none.v_ent = s.v_ent; none.area = s.area; none.vh_new = s.vh_new; none.count = s.count;
+    } else {
+        sediment_release_tables(h);
+    }
+    s = none;
 }
 
 // triangle areas as HostSediment forms them: 0.5*|(x1 - x0)*(y2 - y0) - (x2 - x0)*(y1 - y0)|, no contraction
@@ -234,6 +397,79 @@ void sediment_areas(const Handle *h, const double *vx, const double *vy, std::ve
         const double p = ax*by, q = bx*ay;
         area[k] = 0.5*std::fabs(p - q);
     }
+}
+
+// the Exner tables (vertex lists, areas, the second bed array, the counter), shared by the sediment field and the bedload model
+int exner_tables_build(Handle *h, const char *who)
+{
+    Handle::Sediment &s = h->sed;
+    const int n = h->n_cells, nv = h->n_vertices;
+    if (!s.count) {                                    // (count is allocated last: a failed attempt is released and built again)
+        sediment_release_tables(h);
+        // vertex -> (cell, local node), cells ascending; triangle areas
+        std::vector<int> off(nv + 1, 0);
+        for (size_t j = 0; j < (size_t)3*n; j++) off[h->host_cells[j] + 1]++;
+        for (int v = 0; v < nv; v++) off[v + 1] += off[v];
+        std::vector<int> ent((size_t)3*n), pos_(off.begin(), off.end() - 1);
+        for (int k = 0; k < n; k++)
+            for (int i = 0; i < 3; i++) ent[pos_[h->host_cells[(size_t)3*k + i]]++] = (k << 2) | i;
+        std::vector<double> vx(nv), vy(nv), area;
+        HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+        sediment_areas(h, vx.data(), vy.data(), area);
+        HIP_TRY(h, hipMalloc(&s.v_off, off.size()*sizeof(int)));
+        HIP_TRY(h, hipMalloc(&s.v_ent, ent.size()*sizeof(int)));
+        HIP_TRY(h, hipMalloc(&s.area, (size_t)n*sizeof(double)));
+        HIP_TRY(h, hipMalloc(&s.vh_new, (size_t)nv*sizeof(double)));
+        HIP_TRY(h, hipMemcpy(s.v_off, off.data(), off.size()*sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(s.v_ent, ent.data(), ent.size()*sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(s.area, area.data(), (size_t)n*sizeof(double), hipMemcpyHostToDevice));
+        unsigned *cnt = nullptr;
+        HIP_TRY(h, hipMalloc(&cnt, sizeof(unsigned)));
+        if (hipMemset(cnt, 0, sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(cnt); return fail(h, SWE2D_ERR_HIP, (std::string(who) + ": clearing the counter failed").c_str()); }
+        s.count = cnt;
+    }
+    return SWE2D_OK;
+}
+
+// the three hat-function gradients of every triangle as HostSediment forms them (include/swe2d.h), no contraction: [6][stride]
+void bedload_gradients(const Handle *h, const double *vx, const double *vy, std::vector<double> &grad)
+{
+#pragma clang fp contract(off)
+    const int n = h->n_cells;
+    const size_t S = h->stride;
+    grad.assign(6*S, 0.0);
+    for (int k = 0; k < n; k++) {
+        const int *c = &h->host_cells[(size_t)3*k];
+        const double x0 = vx[c[0]], x1 = vx[c[1]], x2 = vx[c[2]], y0 = vy[c[0]], y1 = vy[c[1]], y2 = vy[c[2]];
+        const double p = (x1 - x0)*(y2 - y0), q = (x2 - x0)*(y1 - y0);
+        const double det = p - q;
+        grad[0*S + k] = (y1 - y2)/det; grad[1*S + k] = (y2 - y0)/det; grad[2*S + k] = (y0 - y1)/det;
+        grad[3*S + k] = (x2 - x1)/det; grad[4*S + k] = (x0 - x2)/det; grad[5*S + k] = (x1 - x0)/det;
+    }
+}
+
+void bedload_release(Handle *h)
+{
+    Handle::Bedload &b = h->bed;
+    if (b.planes) (void)hipFree(b.planes);
+    if (b.grad) (void)hipFree(b.grad);
+    b = Handle::Bedload();
+}
+
+int exner_check(Handle *h, const char *who)
+{
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (!h->sed.on && !h->bed.on)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle has neither a sediment model (swe2d_sediment_set) nor a bedload model (swe2d_bedload_set)");
+    return SWE2D_OK;
+}
+
+int bedload_check(Handle *h, const char *who)
+{
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (!h->bed.on) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle has no bedload model (swe2d_bedload_set)");
+    return SWE2D_OK;
 }
 
 }  // namespace
@@ -258,9 +494,13 @@ int swe2d_impl::sediment_update_launch(Handle *h)
     SweSedArgs a{};
     sediment_fill(h, a);
     a.begin = 0; a.end = h->n_cells;
-    SWE_CHK_SYNC(h->stream);
-    hipLaunchKernelGGL(swe_sediment_coeff_kernel, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
+    if (bedload_fused(h)) {
+        if (int rc = bedload_launch(h, true)) return rc;
+    } else {
+        SWE_CHK_SYNC(h->stream);
+        hipLaunchKernelGGL(swe_sediment_coeff_kernel, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream, a);
+        HIP_TRY(h, hipGetLastError());
+    }
     if (h->sed.eq_markers && h->n_bnd > 0) {
         a.list = h->bnd_cells;
         a.end = h->n_bnd;
@@ -278,21 +518,78 @@ int swe2d_impl::exner_launch(Handle *h)
     Handle::Sediment &s = h->sed;
     SweSedArgs a{};
     sediment_fill(h, a);
-    a.tin = h->tracers[s.tracer].buf[0];
+    a.tin = s.on ? h->tracers[s.tracer].buf[0] : nullptr;
     a.list = s.v_off; a.ent = s.v_ent; a.area = s.area;
     a.out = s.vh_new;
     a.count = s.count;
     a.begin = 0; a.end = h->n_vertices;
-    a.dtf = h->par.dt*s.par.fac;
-    a.min_depth = s.par.min_depth;
+    // (a handle without a sediment field takes the factor and the floor from the bedload parameters)
+    a.dtf = h->par.dt*(s.on ? s.par.fac : h->bed.par.fac);
+    a.min_depth = s.on ? s.par.min_depth : h->bed.par.min_depth;
+    a.contrib = h->bed.on ? h->bed.planes + 6*h->stride : nullptr;
     SWE_CHK_SYNC(h->stream);
-    hipLaunchKernelGGL(swe_exner_kernel, dim3(grid_for(h->n_vertices)), dim3(256), 0, h->stream, a);
+    const dim3 grid(grid_for(h->n_vertices)), block(256);
+    if (s.on && h->bed.on) hipLaunchKernelGGL((swe_exner_kernel<true, true>), grid, block, 0, h->stream, a);
+    else if (s.on) hipLaunchKernelGGL((swe_exner_kernel<true, false>), grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL((swe_exner_kernel<false, true>), grid, block, 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->vh, s.vh_new, (size_t)h->n_vertices*sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SWE2D_OK;
 }
 
-void swe2d_impl::sediment_free(Handle *h) { sediment_release(h); }
+void swe2d_impl::sediment_free(Handle *h) { bedload_release(h); sediment_release(h); }
+
+namespace {
+template <bool COEF>
+void bedload_dispatch(Handle *h, const SweBedArgs &a)
+{
+    const swe2d_bedload_params &p = h->bed.par;
+    const int sw = (p.use_slope_mag_correction ? 1 : 0) | (p.use_angle_correction ? 2 : 0) | (p.use_secondary_current ? 4 : 0);
+    const dim3 grid(grid_for(h->n_cells)), block(256);
+    switch (sw) {
+    case 0: hipLaunchKernelGGL((swe_bedload_kernel<false, false, false, COEF>), grid, block, 0, h->stream, a); break;
+    case 1: hipLaunchKernelGGL((swe_bedload_kernel<true, false, false, COEF>), grid, block, 0, h->stream, a); break;
+    case 2: hipLaunchKernelGGL((swe_bedload_kernel<false, true, false, COEF>), grid, block, 0, h->stream, a); break;
+    case 3: hipLaunchKernelGGL((swe_bedload_kernel<true, true, false, COEF>), grid, block, 0, h->stream, a); break;
+    case 4: hipLaunchKernelGGL((swe_bedload_kernel<false, false, true, COEF>), grid, block, 0, h->stream, a); break;
+    case 5: hipLaunchKernelGGL((swe_bedload_kernel<true, false, true, COEF>), grid, block, 0, h->stream, a); break;
+    case 6: hipLaunchKernelGGL((swe_bedload_kernel<false, true, true, COEF>), grid, block, 0, h->stream, a); break;
+    default: hipLaunchKernelGGL((swe_bedload_kernel<true, true, true, COEF>), grid, block, 0, h->stream, a); break;
+    }
+}
+
+int bedload_launch(Handle *h, bool with_coefficients)
+{
+    Handle::Bedload &b = h->bed;
+    SweBedArgs a{};
+    a.state = h->state[0];
+    a.cv = h->cv; a.nbr = h->nbr; a.vh = h->vh;
+    a.grad = b.grad; a.area = h->sed.area; a.planes = b.planes;
+    a.stride = h->stride;
+    a.n_cells = h->n_cells;
+    a.nonlinear = h->par.use_nonlinear_equations ? 1 : 0;
+    a.g = h->par.g_grav;
+    a.par = b.par;
+    if (with_coefficients) { a.sed_planes = h->sed.planes; a.sed = h->sed.par; }
+    SWE_CHK_SYNC(h->stream);
+    if (with_coefficients) bedload_dispatch<true>(h, a);
+    else bedload_dispatch<false>(h, a);
+    HIP_TRY(h, hipGetLastError());
+    return SWE2D_OK;
+}
+}  // namespace
+
+// the sediment update computes q_b in the coefficient pass's launch: asked for (fuse_with_sediment), and the friction closures of
+// the two models are the same numbers.  Flow and bed do not change between the sediment update and the bedload pass of a step, so
+// the planes are those the separate launch would write.
+bool swe2d_impl::bedload_fused(const Handle *h)
+{
+    const swe2d_bedload_params &b = h->bed.par;
+    const swe2d_sediment_params &s = h->sed.par;
+    return h->sed.on && h->bed.on && b.fuse_with_sediment && b.ks == s.ks && b.ksp == s.ksp && b.kappa == s.kappa;
+}
+
+int swe2d_impl::bedload_update_launch(Handle *h) { return bedload_launch(h, false); }
 
 extern "C" {
 
@@ -318,7 +615,6 @@ int swe2d_sediment_set(swe2d_handle *hh, int tracer_id, const swe2d_sediment_par
     Handle::Tracer &t = h->tracers[tracer_id];
     Handle::Sediment &s = h->sed;
     const size_t S = h->stride, plane_bytes = 3*S*sizeof(double);
-    const int n = h->n_cells, nv = h->n_vertices;
     if (!s.planes) {
         HIP_TRY(h, hipMalloc(&s.planes, 3*plane_bytes));
         HIP_TRY(h, hipMemsetAsync(s.planes, 0, 3*plane_bytes, h->stream));
@@ -329,31 +625,7 @@ int swe2d_sediment_set(swe2d_handle *hh, int tracer_id, const swe2d_sediment_par
         HIP_TRY(h, hipMalloc(&t.source, plane_bytes));
         HIP_TRY(h, hipMemsetAsync(t.source, 0, plane_bytes, h->stream));
     }
-    if (!s.count) {                                    // (count is allocated last: a failed attempt is released and built again)
-        sediment_release_tables(h);
-        // vertex -> (cell, local node), cells ascending; triangle areas
-        std::vector<int> off(nv + 1, 0);
-        for (size_t j = 0; j < (size_t)3*n; j++) off[h->host_cells[j] + 1]++;
-        for (int v = 0; v < nv; v++) off[v + 1] += off[v];
-        std::vector<int> ent((size_t)3*n), pos_(off.begin(), off.end() - 1);
-        for (int k = 0; k < n; k++)
-            for (int i = 0; i < 3; i++) ent[pos_[h->host_cells[(size_t)3*k + i]]++] = (k << 2) | i;
-        std::vector<double> vx(nv), vy(nv), area;
-        HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
-        sediment_areas(h, vx.data(), vy.data(), area);
-        HIP_TRY(h, hipMalloc(&s.v_off, off.size()*sizeof(int)));
-        HIP_TRY(h, hipMalloc(&s.v_ent, ent.size()*sizeof(int)));
-        HIP_TRY(h, hipMalloc(&s.area, (size_t)n*sizeof(double)));
-        HIP_TRY(h, hipMalloc(&s.vh_new, (size_t)nv*sizeof(double)));
-        HIP_TRY(h, hipMemcpy(s.v_off, off.data(), off.size()*sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(s.v_ent, ent.data(), ent.size()*sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(s.area, area.data(), (size_t)n*sizeof(double), hipMemcpyHostToDevice));
-        unsigned *cnt = nullptr;
-        HIP_TRY(h, hipMalloc(&cnt, sizeof(unsigned)));
-        if (hipMemset(cnt, 0, sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(cnt); return fail(h, SWE2D_ERR_HIP, "swe2d_sediment_set: clearing the counter failed"); }
-        s.count = cnt;
-    }
+    if (int rc = exner_tables_build(h, "swe2d_sediment_set")) return rc;
     s.par = *par;
     s.tracer = tracer_id;
     s.on = true;
@@ -443,10 +715,92 @@ int swe2d_sediment_clear(swe2d_handle *hh)
     return SWE2D_OK;
 }
 
+int swe2d_bedload_set(swe2d_handle *hh, const swe2d_bedload_params *par)
+{
+    Handle *h = H(hh);
+    if (!h || !par) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_bedload_set: null argument");
+    if (h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_bedload_set: the sediment model runs on triangles only");
+    if (h->n_owned != h->n_cells) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_bedload_set: the sediment model is not available on partitions");
+    if (h->wd) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_bedload_set: not with wetting-drying (the depth planes are tied to the bed)");
+    if (par->solve_exner && h->n_farms > 0)
+        return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_bedload_set: solve_exner is not available together with tidal turbine farms");
+    if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_bedload_set inside a stream capture");
+    const double pos[] = {par->thetacr, par->shields_den, par->qb_scale, par->ks, par->ksp, par->kappa, par->rho0, par->fac, par->min_depth};
+    for (double x : pos)
+        if (!(x > 0.0) || !std::isfinite(x)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_bedload_set: thetacr, shields_den, qb_scale, ks, ksp, kappa, rho0, fac and min_depth must be positive and finite");
+    if (!std::isfinite(par->beta) || !(par->surbeta2 >= 0.0) || !std::isfinite(par->surbeta2))
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_bedload_set: beta must be finite and surbeta2 >= 0");
+    if (par->use_secondary_current && (!(par->alpha_secc > 0.0) || !std::isfinite(par->alpha_secc)))
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_bedload_set: alpha_secc must be positive with the secondary current");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    Handle::Bedload &b = h->bed;
+    const size_t S = h->stride;
+    const int nv = h->n_vertices;
+    if (int rc = exner_tables_build(h, "swe2d_bedload_set")) return rc;
+    if (!b.grad) {
+        std::vector<double> vx(nv), vy(nv), grad;
+        HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+        bedload_gradients(h, vx.data(), vy.data(), grad);
+        double *g = nullptr;
+        HIP_TRY(h, hipMalloc(&g, 6*S*sizeof(double)));
+        if (hipMemcpy(g, grad.data(), 6*S*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(g);
+            return fail(h, SWE2D_ERR_HIP, "swe2d_bedload_set: uploading the gradient table failed");
+        }
+        b.grad = g;
+    }
+    if (!b.planes) {
+        HIP_TRY(h, hipMalloc(&b.planes, 9*S*sizeof(double)));
+        HIP_TRY(h, hipMemsetAsync(b.planes, 0, 9*S*sizeof(double), h->stream));
+    }
+    b.par = *par;
+    b.on = true;
+    return SWE2D_OK;
+}
+
+int swe2d_bedload_update(swe2d_handle *hh)
+{
+    Handle *h = H(hh);
+    if (int rc = bedload_check(h, "swe2d_bedload_update")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return bedload_update_launch(h);
+}
+
+int swe2d_bedload_read(swe2d_handle *hh, double *qbx, double *qby, double *contrib)
+{
+    Handle *h = H(hh);
+    if (int rc = bedload_check(h, "swe2d_bedload_read")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    double *dst[3] = {qbx, qby, contrib};
+    for (int q = 0; q < 3; q++) {
+        if (!dst[q]) continue;
+        hipLaunchKernelGGL(swe_planes_to_nodal, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream,
+                           h->bed.planes + (size_t)3*q*h->stride, h->stage_eta, h->stride, h->n_cells, 3);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(dst[q], h->stage_eta, (size_t)3*h->n_cells*sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return SWE2D_OK;
+}
+
+int swe2d_bedload_clear(swe2d_handle *hh)
+{
+    Handle *h = H(hh);
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (!h->bed.on) return SWE2D_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    bedload_release(h);
+    if (!h->sed.on) sediment_release_tables(h);
+    return SWE2D_OK;
+}
+
 int swe2d_exner_step(swe2d_handle *hh)
 {
     Handle *h = H(hh);
-    if (int rc = sediment_check(h, "swe2d_exner_step")) return rc;
+    if (int rc = exner_check(h, "swe2d_exner_step")) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     return exner_launch(h);
 }
@@ -454,7 +808,7 @@ int swe2d_exner_step(swe2d_handle *hh)
 int swe2d_exner_skipped(swe2d_handle *hh, int64_t *n_skipped)
 {
     Handle *h = H(hh);
-    if (int rc = sediment_check(h, "swe2d_exner_skipped")) return rc;
+    if (int rc = exner_check(h, "swe2d_exner_skipped")) return rc;
     if (!n_skipped) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     unsigned c = 0;

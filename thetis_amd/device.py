@@ -1039,6 +1039,35 @@ class Swe2dDevice(object):
     def exner_step(self):
         self._ck(self.lib.swe2d_exner_step(self.h))
 
+    # -- bedload transport in the Exner update (sediment_model.bedload_device_parameters)
+    def bedload_set(self, params, open_markers=()):
+        """switches the bedload model on; ``params``: the fields of ``_lib.BedloadParams`` as a dict without ``open_markers``,
+        which is built here from the mesh markers in ``open_markers`` (markers the mesh does not have are ignored)"""
+        p = _lib.BedloadParams()
+        for name, ctype in _lib.BedloadParams._fields_:
+            if name != 'open_markers':
+                setattr(p, name, (int if ctype is ctypes.c_int32 else float)(params.get(name, 0) if name == 'fuse_with_sediment'
+                                                                              else params[name]))
+        mask = 0
+        for m in open_markers:
+            if int(m) in self._marker_slot:
+                mask |= 1 << self._marker_slot[int(m)]
+        p.open_markers = mask
+        self._ck(self.lib.swe2d_bedload_set(self.h, ctypes.byref(p)))
+
+    def bedload_update(self):
+        """q_b and its contributions to the Exner update from the current flow and bed"""
+        self._ck(self.lib.swe2d_bedload_update(self.h))
+
+    def bedload_read(self):
+        """(qbx, qby, contributions), each (N, 3) nodal"""
+        out = [np.empty((self.n_cells, self.npc)) for _ in range(3)]
+        self._ck(self.lib.swe2d_bedload_read(self.h, *[_ptr(a) for a in out]))
+        return tuple(self._nodal_out(a) for a in out)
+
+    def bedload_clear(self):
+        self._ck(self.lib.swe2d_bedload_clear(self.h))
+
     def exner_skipped(self):
         n = ctypes.c_int64(0)
         self._ck(self.lib.swe2d_exner_skipped(self.h, ctypes.byref(n)))

@@ -16,7 +16,7 @@ from .log import print_output
 from .options import Constant
 
 __all__ = ['SedimentModel', 'SedimentEquation2D', 'HostSediment', 'sediment_constants', 'closures', 'check_sediment_options', 'device_parameters',
-           'EXNER_MIN_DEPTH']
+           'bedload_constants', 'bedload_closures', 'bedload_device_parameters', 'open_bedload_markers', 'EXNER_MIN_DEPTH']
 
 EXNER_MIN_DEPTH = 1e-3       # a vertex whose depth an Exner update would take below this keeps its bed (and is counted)
 
@@ -53,7 +53,7 @@ def sediment_constants(average_size, bed_reference_height, viscosity, sediment_d
         raise ValueError('dstar value less than 1')
     thetacr = _thetacr(dstar)
     a = ks/2
-    c = dict(average_size=d, R=R, dstar=dstar, thetacr=thetacr, taucr=(rhos - rho0)*g*d*thetacr,
+    c = dict(average_size=d, R=R, rhos=rhos, dstar=dstar, thetacr=thetacr, taucr=(rhos - rho0)*g*d*thetacr,
              ws=float(_settling_velocity(d, R, g, nu)), a=a, ksp=3*d, ks=ks, rho0=float(rho0), g=float(g), kappa=float(kappa),
              fac=float(morfac)/(1 - float(porosity)))
     c['erosion_factor'] = 0.015*(d/a)/(dstar**0.3)
@@ -67,16 +67,7 @@ def closures(c, u, v, H):
     u, v, H = (np.asarray(x, dtype=np.float64) for x in (u, v, H))
     kappa, ws, ks, ksp, a = c['kappa'], c['ws'], c['ks'], c['ksp'], c['a']
     with np.errstate(divide='ignore'):
-        unorm = u*u + v*v
-        hc = np.where(H > 0.001, H, 0.001)
-        ax = 11.036*hc/ks
-        aux = np.where(ax > 1.001, ax, 1.001)
-        lq = np.log(aux)/kappa
-        qfc = 2.0/(lq*lq)
-        deep = H > ksp
-        lc = (1.0/kappa)*np.log(11.036*np.where(deep, H, ksp)/ksp)
-        cfactor = np.where(deep, 2.0/(lc*lc), 0.0)
-        mu = np.where(qfc > 0.0, cfactor/qfc, 0.0)
+        unorm, qfc, cfactor, mu = _friction(c, u, v, H)
         B = np.where(a > H, 1.0, a/np.where(a > H, 1.0, H))
         ustar = np.sqrt(0.5*qfc*unorm)
         rouse = ws/(kappa*ustar) - 1.0
@@ -95,6 +86,113 @@ def closures(c, u, v, H):
     return dict(qfc=qfc, cfactor=cfactor, mu=mu, B=B, ustar=ustar, rouse_number=rouse, intermediate_step=step,
                 integrated_rouse=integrated_rouse, transport_stage_param=T, erosion_concentration=erosion_concentration,
                 erosion=E, deposition=D, equilibrium=E/D)
+
+
+def _friction(c, u, v, H):
+    """unorm, qfc, cfactor, mu: the lines of ``closures`` that the bedload shares (swe_sediment_friction on the device)"""
+    kappa, ks, ksp = c['kappa'], c['ks'], c['ksp']
+    unorm = u*u + v*v
+    hc = np.where(H > 0.001, H, 0.001)
+    ax = 11.036*hc/ks
+    aux = np.where(ax > 1.001, ax, 1.001)
+    lq = np.log(aux)/kappa
+    qfc = 2.0/(lq*lq)
+    deep = H > ksp
+    lc = (1.0/kappa)*np.log(11.036*np.where(deep, H, ksp)/ksp)
+    cfactor = np.where(deep, 2.0/(lc*lc), 0.0)
+    mu = np.where(qfc > 0.0, cfactor/qfc, 0.0)
+    return unorm, qfc, cfactor, mu
+
+
+def bedload_constants(c, slope_effect_parameter=1.3, slope_effect_angle_parameter=2/3, secondary_current_parameter=0.75,
+                      use_slope_mag_correction=True, use_angle_correction=True, use_secondary_current=False):
+    """``sediment_constants`` plus what the bedload closures read (sediment_model.py:104-119, 222-310)"""
+    d, g = c['average_size'], c['g']
+    b = dict(c)
+    b.update(beta=float(slope_effect_parameter), surbeta2=float(slope_effect_angle_parameter),
+             alpha_secc=float(secondary_current_parameter), shields_den=(c['rhos'] - c['rho0'])*g*d,
+             qb_scale=float(np.sqrt(g*c['R']*d**3)), use_slope_mag_correction=bool(use_slope_mag_correction),
+             use_angle_correction=bool(use_angle_correction), use_secondary_current=bool(use_secondary_current))
+    return b
+
+
+def bedload_closures(b, u, v, H, hx, hy, ex, ey):
+    """Meyer-Peter-Mueller transport (qbx, qby) with the slope and secondary current corrections at points with velocity (u, v),
+    total depth H, bed gradient (hx, hy) and free-surface gradient (ex, ey): arrays that broadcast to one shape.  Operation by
+    operation what swe_bedload_node does on the device (include/swe2d.h has the formulas); every conditional is a select, and a
+    divisor that can vanish where nothing moves is replaced by 1 there."""
+    u, v, H, hx, hy, ex, ey = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (u, v, H, hx, hy, ex, ey)))
+    unorm, qfc, _, mu = _friction(b, u, v, H)
+    stress = b['rho0']*0.5*qfc*unorm
+    thetaprime = mu*stress/b['shields_den']
+    moves = thetaprime > b['thetacr']
+    x = np.where(moves, thetaprime - b['thetacr'], 0.0)
+    phi = np.where(moves, 8.0*x*np.sqrt(x), 0.0)
+    sn = np.where(moves, np.sqrt(unorm), 1.0)
+    calfa, salfa = u/sn, v/sn
+    slopecoef = 1.0 + b['beta']*(hx*calfa + hy*salfa) if b['use_slope_mag_correction'] else np.ones_like(u)
+    ca, sa = calfa, salfa
+    if b['use_angle_correction']:
+        cparam = b['shields_den']*(b['surbeta2']*b['surbeta2'])
+        tt1 = np.sqrt(cparam/np.where(stress > 1e-10, stress, 1e-10))
+        aa, bb = salfa + tt1*hy, calfa + tt1*hx
+        comb = np.sqrt(aa*aa + bb*bb)
+        nrm = np.where(comb > 1e-10, comb, 1e-10)
+        ca, sa = bb/nrm, aa/nrm
+    factor, live = slopecoef, phi > 0.0
+    if b['use_secondary_current']:
+        vs = u*ey - v*ex
+        tdf = 7.0*b['g']*b['rho0']*H*qfc/(2.0*b['alpha_secc']*np.where(moves, unorm, 1.0))
+        t1 = stress*slopecoef*ca + v*tdf*vs
+        t2 = stress*slopecoef*sa - u*tdf*vs
+        t4 = np.sqrt(t1*t1 + t2*t2)
+        t4s = np.where(t4 > 0.0, t4, 1.0)
+        factor = t4/np.where(moves, stress, 1.0)
+        ca, sa = t1/t4s, t2/t4s
+        live = live & (t4 > 0.0)
+    qtot = factor*phi*b['qb_scale']
+    return np.where(live, qtot*ca, 0.0), np.where(live, qtot*sa, 0.0)
+
+
+def bedload_device_parameters(b, solve_exner=True, min_depth=EXNER_MIN_DEPTH, fuse_with_sediment=False):
+    """``bedload_constants`` -> the fields of include/swe2d.h swe2d_bedload_params but ``open_markers`` (Swe2dDevice.bedload_set
+    builds the mask from a list of markers)"""
+    p = {k: b[k] for k in ('beta', 'surbeta2', 'alpha_secc', 'thetacr', 'shields_den', 'qb_scale', 'ks', 'ksp', 'kappa', 'rho0', 'fac')}
+    p.update(min_depth=float(min_depth), solve_exner=int(bool(solve_exner)), fuse_with_sediment=int(bool(fuse_with_sediment)),
+             **{k: int(b[k]) for k in ('use_slope_mag_correction', 'use_angle_correction', 'use_secondary_current')})
+    return p
+
+
+def _is_zero(v):
+    """``float(v) == 0.0`` of the reference's rule; a Function, a tidal forcing or anything without a float() counts as non-zero"""
+    try:
+        return float(v) == 0.0
+    except (TypeError, ValueError):
+        return False
+
+
+def open_bedload_markers(bnd_functions, markers=None):
+    """The markers open to the bedload transport by the reference's rule (exner_eq.py:113-125) on the shallow-water boundary dict:
+    a marker absent from the dict is closed; so is one with a key other than 'elev' / 'uv' whose value is zero, or with a 'uv' whose
+    components are all zero; every other marker is open.  ``markers``: restrict to these."""
+    out = []
+    for marker, funcs in (bnd_functions or {}).items():
+        if funcs is None or (markers is not None and marker not in markers):
+            continue
+        closed = False
+        for key, val in funcs.items():
+            if key not in ('elev', 'uv'):
+                closed = closed or _is_zero(val)
+            elif key == 'uv':
+                try:
+                    comps = None if isinstance(val, Function) else list(val)
+                except TypeError:
+                    comps = None                                         # not a sequence of numbers: non-zero
+                if comps is not None and all(_is_zero(j) for j in comps):
+                    closed = True
+        if not closed:
+            out.append(marker)
+    return out
 
 
 def device_parameters(c, conservative=False, solve_exner=False, min_depth=EXNER_MIN_DEPTH):
@@ -120,6 +218,11 @@ class HostSediment(object):
         p = (x[:, 1] - x[:, 0])*(y[:, 2] - y[:, 0])
         q = (x[:, 2] - x[:, 0])*(y[:, 1] - y[:, 0])
         self.area = 0.5*np.abs(p - q)
+        # the gradients of the three hat functions, (N, 3) each, formed as the library's host part forms them (include/swe2d.h)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            det = p - q
+            self.grad_x = np.stack([(y[:, 1] - y[:, 2])/det, (y[:, 2] - y[:, 0])/det, (y[:, 0] - y[:, 1])/det], axis=1)
+            self.grad_y = np.stack([(x[:, 2] - x[:, 1])/det, (x[:, 0] - x[:, 2])/det, (x[:, 1] - x[:, 0])/det], axis=1)
         self.n_vertices = xy.shape[0]
         # vertex -> (cell, local node), cells ascending
         flat = self.cells.reshape(-1)
@@ -154,10 +257,52 @@ class HostSediment(object):
         """what the 'equilibrium' facets of the per-facet value table hold at the nodes of a cell"""
         return equilibrium*self.depth(eta, bath) if self.conservative else equilibrium
 
-    def exner(self, E, D, S, eta, bath, dt):
-        """one bed update: the new vertex bathymetry (vertices whose depth would fall below the floor keep theirs)"""
+    def gradient(self, nodal):
+        """cell-constant gradient of the P1 interpolant of (N, 3) nodal values: (gx, gy), each (N,)"""
+        f, gx, gy = np.asarray(nodal, dtype=np.float64), self.grad_x, self.grad_y
+        return ((f[:, 0]*gx[:, 0] + f[:, 1]*gx[:, 1]) + f[:, 2]*gx[:, 2],
+                (f[:, 0]*gy[:, 0] + f[:, 1]*gy[:, 1]) + f[:, 2]*gy[:, 2])
+
+    def bedload(self, uv, eta, bath, constants=None):
+        """nodal bedload transport (N, 3, 2) from nodal ``uv`` (N, 3, 2), ``eta`` (N, 3) and the vertex bathymetry; ``constants``:
+        ``bedload_constants`` (default: this object's constants, which then must hold them)"""
+        b = self.c if constants is None else constants
+        uv, eta = np.asarray(uv, dtype=np.float64), np.asarray(eta, dtype=np.float64)
+        hx, hy = self.gradient(np.asarray(bath, dtype=np.float64)[self.cells])
+        ex, ey = self.gradient(eta) if self.nonlinear else (np.zeros_like(hx), np.zeros_like(hy))
+        qx, qy = bedload_closures(b, uv[..., 0], uv[..., 1], self.depth(eta, bath), hx[:, None], hy[:, None], ex[:, None], ey[:, None])
+        return np.stack([qx, qy], axis=2)
+
+    def bedload_contributions(self, qb, cell_nbr=None, open_markers=0):
+        """(N, 3): what each cell adds at its three nodes to the integral of div q_b against the vertex hat functions, the boundary
+        integral over the open facets included.  ``cell_nbr``: (N, 3) facet codes (facet f joins the nodes f and (f+1)%3; a boundary
+        facet carries minus its marker); ``open_markers``: bit m set = marker m is open, or an iterable of markers."""
+        qb = np.asarray(qb, dtype=np.float64)
+        qx, qy, A, gx, gy = qb[..., 0], qb[..., 1], self.area, self.grad_x, self.grad_y
+        if not isinstance(open_markers, (int, np.integer)):
+            open_markers = sum(1 << int(m) for m in set(open_markers))
+        mx = ((qx[:, 0] + qx[:, 1]) + qx[:, 2])/3.0
+        my = ((qy[:, 0] + qy[:, 1]) + qy[:, 2])/3.0
+        c = [-(A*(mx*gx[:, i] + my*gy[:, i])) for i in range(3)]
+        if cell_nbr is not None and open_markers:
+            nbr = np.asarray(cell_nbr, dtype=np.int64)
+            for f in range(3):
+                b, o = (f + 1) % 3, (f + 2) % 3
+                slot = np.where(nbr[:, f] < 0, -nbr[:, f], 0)
+                is_open = (nbr[:, f] < 0) & (slot < 32) & (((int(open_markers) >> np.minimum(slot, 31)) & 1) == 1)
+                Nx, Ny = -((2.0*A)*gx[:, o]), -((2.0*A)*gy[:, o])
+                ta = ((2.0*qx[:, f] + qx[:, b])*Nx + (2.0*qy[:, f] + qy[:, b])*Ny)/6.0
+                tb = ((2.0*qx[:, b] + qx[:, f])*Nx + (2.0*qy[:, b] + qy[:, f])*Ny)/6.0
+                c[f] = np.where(is_open, c[f] + ta, c[f])
+                c[b] = np.where(is_open, c[b] + tb, c[b])
+        return np.stack(c, axis=1)
+
+    def exner(self, E, D, S, eta, bath, dt, bedload=None):
+        """one bed update: the new vertex bathymetry (vertices whose depth would fall below the floor keep theirs).  ``bedload``:
+        the (N, 3) contributions of ``bedload_contributions``, gathered separately and added to the numerator; ``E`` = None: no
+        sediment field (bedload only)"""
         bath = np.asarray(bath, dtype=np.float64)
-        r = self.net_erosion(E, D, S, eta, bath)
+        r = self.net_erosion(E, D, S, eta, bath) if E is not None else np.zeros(self.cells.shape)
         dtf = dt*self.c['fac']
         w12, w3 = self.area/12.0, self.area/3.0
         eta = np.asarray(eta, dtype=np.float64)
@@ -172,7 +317,12 @@ class HostSediment(object):
         eta_min = np.full(self.n_vertices, 1e300)
         np.minimum.at(eta_min, vert, eta[k, i])
         used = den > 0.0
-        b = bath + (dtf*num)/np.where(used, den, 1.0)
+        if bedload is not None:
+            nb = np.zeros(self.n_vertices)
+            np.add.at(nb, vert, np.asarray(bedload, dtype=np.float64)[k, i])
+            b = bath + (dtf*(num + nb))/np.where(used, den, 1.0)
+        else:
+            b = bath + (dtf*num)/np.where(used, den, 1.0)
         ok = used & ((eta_min + b if self.nonlinear else b) >= self.min_depth)
         self.n_skipped += int((used & ~ok).sum())
         new = np.where(ok, b, bath)
@@ -182,7 +332,10 @@ class HostSediment(object):
 def _constant_value(name, v):
     """a Constant / number of the sediment options; Functions and expressions are not on this path"""
     if isinstance(v, (int, float, np.floating, Constant)):
-        return float(v)
+        try:
+            return float(v)
+        except TypeError:                       # (a vector Constant: what the options make of an array)
+            pass
     raise NotImplementedError('sediment_model_options.{:} must be a Constant on the device path (a spatially varying value '
                               'is not implemented)'.format(name))
 
@@ -192,16 +345,21 @@ def check_sediment_options(options, mesh2d=None, comm=None, tidal_farms=False):
     (``sediment_constants``).  Called when the equations are built."""
     from .shallowwater_eq import physical_constants
     so = options.sediment_model_options
-    for name in ('use_bedload', 'use_sediment_slide', 'use_secondary_current'):
-        if getattr(so, name):
-            raise NotImplementedError('sediment_model_options.{:} is not implemented: this build runs the suspended load only '
-                                      '(bedload, slide and secondary current differentiate the bed)'.format(name))
+    if so.use_sediment_slide:
+        raise NotImplementedError('sediment_model_options.use_sediment_slide is not implemented: this build runs the suspended load '
+                                  'and the bedload transport (the slide is a diffusion of the bed of its own)')
+    if so.use_bedload and not so.solve_exner:
+        raise NotImplementedError('sediment_model_options.use_bedload without solve_exner is not implemented: the bedload transport '
+                                  'enters the bed update only, and this build refuses an option it would ignore')
+    if so.use_secondary_current and not so.use_bedload:
+        raise NotImplementedError('sediment_model_options.use_secondary_current without use_bedload is not implemented: the secondary '
+                                  'current corrects the bedload transport only')
     if so.solve_suspended_sediment and so.use_advective_velocity_correction:
         raise NotImplementedError('sediment_model_options.use_advective_velocity_correction=True is not implemented (the tracer '
                                   'kernels take a scalar velocity factor): set it False')
-    if so.solve_exner and not so.solve_suspended_sediment:
-        raise NotImplementedError('sediment_model_options.solve_exner without solve_suspended_sediment has no source on this path '
-                                  '(use_bedload is not implemented)')
+    if so.solve_exner and not so.solve_suspended_sediment and not so.use_bedload:
+        raise NotImplementedError('sediment_model_options.solve_exner without solve_suspended_sediment and without use_bedload: the '
+                                  'bed update has no source (set one of the two)')
     if options.use_wetting_and_drying:
         raise NotImplementedError('sediment_model_options.solve_suspended_sediment / solve_exner with use_wetting_and_drying is not '
                                   'implemented: the sediment kernels take H = eta + h, not the wetting-drying depth, and the depth '
@@ -229,10 +387,16 @@ def check_sediment_options(options, mesh2d=None, comm=None, tidal_farms=False):
             for name in ('average_sediment_size', 'bed_reference_height', 'porosity', 'sediment_density')}
     nu = _constant_value('morphological_viscosity' if so.morphological_viscosity is not None else 'horizontal_viscosity (read by the '
                          'sediment model)', nu)
-    return sediment_constants(vals['average_sediment_size'], vals['bed_reference_height'], nu, vals['sediment_density'],
-                              rho0=float(physical_constants['rho0']), g=float(physical_constants['g_grav']),
-                              kappa=float(physical_constants['von_karman']), porosity=vals['porosity'],
-                              morfac=float(so.morphological_acceleration_factor))
+    c = sediment_constants(vals['average_sediment_size'], vals['bed_reference_height'], nu, vals['sediment_density'],
+                           rho0=float(physical_constants['rho0']), g=float(physical_constants['g_grav']),
+                           kappa=float(physical_constants['von_karman']), porosity=vals['porosity'],
+                           morfac=float(so.morphological_acceleration_factor))
+    if so.use_bedload:
+        par = {name: _constant_value(name, getattr(so, name))
+               for name in ('slope_effect_parameter', 'slope_effect_angle_parameter', 'secondary_current_parameter')}
+        c = bedload_constants(c, par['slope_effect_parameter'], par['slope_effect_angle_parameter'], par['secondary_current_parameter'],
+                              so.use_slope_mag_correction, so.use_angle_correction, so.use_secondary_current)
+    return c
 
 
 class SedimentEquation2D(object):
@@ -274,9 +438,9 @@ class SedimentModel(object):
         self.use_advective_velocity_correction = so.use_advective_velocity_correction
         self.use_secondary_current = so.use_secondary_current
         self.constants = check_sediment_options(options, mesh2d, comm, tidal_farms)
-        if self.use_angle_correction:
+        if self.use_angle_correction and not self.use_bedload:
             print_output('WARNING: Slope effect angle correction only applies to bedload transport which is not used in this simulation')
-        if self.use_slope_mag_correction:
+        if self.use_slope_mag_correction and not self.use_bedload:
             print_output('WARNING: Slope effect magnitude correction only applies to bedload transport which is not used in this simulation')
         c = self.constants
         self.average_size, self.bed_reference_height, self.rhos = so.average_sediment_size, so.bed_reference_height, so.sediment_density
@@ -287,16 +451,40 @@ class SedimentModel(object):
                                  nonlinear=bool(getattr(depth, 'use_nonlinear_equations', options.use_nonlinear_equations)))
         self._device = None
         self._planes = None
+        self._qb = None
+        self.bnd_functions = {}                 # the shallow-water boundary dict: which markers the bedload transport leaves through
 
     def device_parameters(self):
         return device_parameters(self.constants, self.conservative, self.options.sediment_model_options.solve_exner)
+
+    # q_b in the launch of the coefficient pass (swe2d_bedload_params.fuse_with_sediment): measured faster than a launch of its own
+    # (DESIGN.md 5h), the same bits; without a sediment field there is no coefficient pass and the switch does nothing
+    fuse_bedload = True
+
+    def bedload_device_parameters(self):
+        return bedload_device_parameters(self.constants, self.options.sediment_model_options.solve_exner,
+                                         fuse_with_sediment=self.fuse_bedload)
+
+    def open_markers(self):
+        """the mesh markers open to the bedload transport (``open_bedload_markers`` on the shallow-water boundary dict)"""
+        return open_bedload_markers(self.bnd_functions, markers=list(self.mesh2d.boundary_markers))
 
     def bind_device(self, device, tracer_id):
         """the sediment field is tracer ``tracer_id`` of ``device``: the passes run there and the planes are read back on demand
         (a device class without ``sediment_set`` is not bound: the terms come from ``HostSediment``)"""
         if hasattr(device, 'sediment_set'):
+            if self.use_bedload and not hasattr(device, 'bedload_set'):
+                raise NotImplementedError('sediment_model_options.use_bedload: the device class has the sediment passes but not the '
+                                          'bedload pass')
             device.sediment_set(tracer_id, self.device_parameters())
+            if self.use_bedload:
+                device.bedload_set(self.bedload_device_parameters(), self.open_markers())
             self._device = device
+
+    def bind_bedload_device(self, device):
+        """a run without a sediment field: the bedload pass and the bed update run on ``device``"""
+        device.bedload_set(self.bedload_device_parameters(), self.open_markers())
+        self._device = device
 
     @property
     def on_device(self):
@@ -308,6 +496,9 @@ class SedimentModel(object):
 
     def update(self):
         """refresh the terms from the current ``uv`` and ``elev`` (once per time step: the coefficients are frozen over it)"""
+        self._qb = None
+        if not self.solve_suspended_sediment:   # (bedload only: no coefficient planes)
+            return
         if self._device is not None:
             self._device.sediment_update()
             self._planes = None
@@ -321,6 +512,35 @@ class SedimentModel(object):
             else:
                 self._planes = self._device.sediment_read()
         return self._planes
+
+    def update_bedload(self):
+        """refresh q_b from the current ``uv``, ``elev`` and bed (once per time step, after the sediment step and the limiter);
+        returns the contributions to the Exner update on the host path, None on the device"""
+        if self._device is not None:
+            self._device.bedload_update()
+            self._qb = None
+            return None
+        self._qb = self.host.bedload(self.uv.cell_node_values(), self.elev.cell_node_values(), self._bathymetry())
+        slot = {m: i + 1 for i, m in enumerate(sorted(int(m) for m in self.mesh2d.boundary_markers))}
+        nbr = np.asarray(self.mesh2d.cell_nbr, dtype=np.int64)
+        lut = np.zeros(max(slot, default=0) + 1, dtype=np.int64)
+        for m, s in slot.items():
+            lut[m] = s
+        nbr = np.where(nbr < 0, -lut[np.where(nbr < 0, -nbr, 0)], nbr)
+        return self.host.bedload_contributions(self._qb, nbr, [slot[int(m)] for m in self.open_markers()])
+
+    def get_bedload_term(self, bathymetry=None):
+        """nodal bedload transport (qbx, qby), each (N, 3), of the last update (``bathymetry``: the reference's argument; the bed is
+        explicit here and the transport is that of the current one)"""
+        if not self.use_bedload:
+            raise ValueError('sediment_model_options.use_bedload is off')
+        if self._qb is None:
+            if self._device is not None:
+                qx, qy, _ = self._device.bedload_read()
+                self._qb = np.stack([qx, qy], axis=2)
+            else:
+                self.update_bedload()
+        return self._qb[..., 0], self._qb[..., 1]
 
     def get_erosion_term(self):
         """(depth-integrated) erosion at the DG nodes"""

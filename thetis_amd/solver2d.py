@@ -217,14 +217,17 @@ class FlowSolver2d(object):
             velocity, elevation = self.fields.solution_2d.subfunctions
             self.sediment_model = so.sediment_model_class(self.options, self.mesh2d, velocity, elevation, self.depth,
                                                           comm=self.comm, tidal_farms=bool(self.tidal_farms))
+            # (bedload: which boundaries the transport leaves through is read from the shallow-water boundary dict, exner_eq.py:113-125)
+            self.sediment_model.bnd_functions = self.bnd_functions['shallow_water']
             if so.solve_exner:
                 b = self.fields.bathymetry_2d
                 if not isinstance(b, Function) or b.function_space().family != 'CG':
                     raise NotImplementedError('sediment_model_options.solve_exner needs bathymetry_2d as a CG-P1 Function (the bed '
                                               'is evolved at the vertices)')
                 b._pull_hook = self._pull_bathymetry
-            self.equations.sediment = SedimentEquation2D(self.function_spaces.Q_2d, self.depth, self.options, self.sediment_model,
-                                                         conservative=so.use_sediment_conservative_form)
+            if so.solve_suspended_sediment:
+                self.equations.sediment = SedimentEquation2D(self.function_spaces.Q_2d, self.depth, self.options, self.sediment_model,
+                                                             conservative=so.use_sediment_conservative_form)
         self.solve_tracer = len(self.options.tracer) > 0
         for label in self.options.tracer:
             self.equations[label] = TracerEquation2D(label, self.function_spaces.Q_2d, self.depth, self.options)
@@ -325,8 +328,10 @@ class FlowSolver2d(object):
                                       "explicit device path; use 'SSPRK33' or 'ForwardEuler'".format(name))
         sediment_steppers = {'SSPRK33': coupled_timeintegrator_2d.DeviceSedimentSSPRK33,
                              'ForwardEuler': coupled_timeintegrator_2d.DeviceSedimentForwardEuler}
-        solve_sediment = self.sediment_model is not None
-        if self.solve_tracer or solve_sediment:
+        so = self.options.sediment_model_options
+        solve_sediment = self.sediment_model is not None and so.solve_suspended_sediment
+        bed_only = self.sediment_model is not None and not so.solve_suspended_sediment      # bedload + Exner, no sediment field
+        if self.solve_tracer or solve_sediment or bed_only:
             if self.solve_tracer and self.options.tracer_timestepper_type not in tracer_steppers:
                 raise NotImplementedError("tracer_timestepper_type {!r} is outside the explicit device path; use "
                                           "'SSPRK33' or 'ForwardEuler'".format(self.options.tracer_timestepper_type))
@@ -340,7 +345,8 @@ class FlowSolver2d(object):
             if solve_sediment:                  # last: stepped after the user's tracers
                 so = self.options.sediment_model_options
                 tracers['sediment_2d'] = self.get_sediment_timestepper(sediment_steppers[so.sediment_timestepper_type], swe)
-            self.timestepper = coupled_timeintegrator_2d.GeneralCoupledTimeIntegrator2D(self, swe, tracers)
+            bed = coupled_timeintegrator_2d.BedloadStepper(self.sediment_model, swe.device, self.dt) if bed_only else None
+            self.timestepper = coupled_timeintegrator_2d.GeneralCoupledTimeIntegrator2D(self, swe, tracers, bed=bed)
         else:
             self.timestepper = self.get_swe_timestepper(steppers[name])
         print_output('Using time integrator: {:}'.format(self.timestepper.__class__.__name__))
@@ -409,7 +415,9 @@ class FlowSolver2d(object):
                 raise AssertionError('Unknown tracer label {:}'.format(label))
             self.fields[label].project(expression)
         self.timestepper.initialize(self.fields.solution_2d)
-        if self.sediment_model is not None:
+        if self.sediment_model is not None and self.sediment_model.use_bedload:
+            self.sediment_model.update_bedload()            # q_b of the initial flow (get_bedload_term before the first step)
+        if self.sediment_model is not None and self.sediment_model.solve_suspended_sediment:
             # the model on the initial flow; without an initial field the sediment starts in equilibrium (solver2d.py:772-783)
             self.timestepper.tracers['sediment_2d'].sediment_update()
             if sediment is not None:
@@ -601,7 +609,7 @@ class FlowSolver2d(object):
             if o.check_tracer_overshoot:
                 checks.append(callback.TracerOvershootCallBack(label, self))
         so = o.sediment_model_options
-        if self.sediment_model is not None:
+        if self.sediment_model is not None and so.solve_suspended_sediment:
             if so.check_sediment_conservation:
                 make = (callback.ConservativeTracerMassConservation2DCallback if so.use_sediment_conservative_form
                         else callback.TracerMassConservation2DCallback)

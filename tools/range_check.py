@@ -261,7 +261,11 @@ def exercise(only=None):
                 # value table over the boundary-cell list; the source kernel runs in front of every stage launch (whole mesh, ragged
                 # sub-ranges, ForwardEuler); the Exner kernel gathers over the vertex -> (cell, node) list, reads the cell areas and
                 # writes the second bathymetry array.  Both forms, a plain tracer next to the field, the batch.  Quadrilaterals: refused.
-                from thetis_amd.sediment_model import device_parameters, sediment_constants
+                # Bedload (swe_bedload_kernel): reads the state planes, the cell vertices, the bathymetry, the gradient table, the areas
+                # and the facet codes, writes the six q_b and three contribution planes, which the Exner kernel gathers: every switch
+                # combination next to the sediment field, the launch fused with the coefficient pass, the batch, and a handle with
+                # bedload alone stepped by swe2d_advance.
+                from thetis_amd.sediment_model import bedload_constants, bedload_device_parameters, device_parameters, sediment_constants
                 cs = sediment_constants(160e-6, 0.025, 1e-6, morfac=50.0)
                 plain = dev.add_tracer()
                 tid = dev.add_tracer()
@@ -295,7 +299,25 @@ def exercise(only=None):
                         assert np.isfinite(dev.tracer_get_state(tid)).all() and np.isfinite(dev.get_bathymetry()).all(), (name, variant)
                         assert np.isfinite(dev.sediment_read_bc()).all() and np.isfinite(dev.tracer_get_source(tid)).all()
                         dev.exner_skipped()
-                        dev.sediment_clear()
+                        for sw in range(8):
+                            cb = bedload_constants(cs, 1.3, 2/3, 0.75, bool(sw & 1), bool(sw & 2), bool(sw & 4))
+                            for fuse in (0, 1):
+                                dev.bedload_set(dict(bedload_device_parameters(cb, True), fuse_with_sediment=fuse), markers[:1])
+                                dev.sediment_update()
+                                dev.bedload_update()
+                                dev.exner_step()
+                                n_launch += 4
+                                assert all(np.isfinite(a).all() for a in dev.bedload_read()), (name, variant, sw, fuse)
+                            dev.advance_coupled(2, tracer_only=False, use_limiter=True)
+                            n_launch += 2*(3 + 6 + 2 + 6 + 3 + 1 + 1)
+                        assert np.isfinite(dev.get_bathymetry()).all(), (name, variant)
+                        dev.sediment_clear()                    # bedload alone from here: the Exner tables stay
+                        dev.bedload_update()
+                        dev.exner_step()
+                        dev.advance(2)
+                        assert np.isfinite(dev.get_bathymetry()).all() and not dev.flow_supported(), (name, variant)
+                        dev.bedload_clear()
+                        n_launch += 2 + 2*5
                         n_launch += 2 + 3*2 + 6*2 + 2 + 3 + 1 + 2*(3 + 6 + 2 + 6 + 3 + 1)
             if variant == 'sections':
                 # section transports (csrc/swe2d_sections.hip): swe_section_transport_kernel reads the piece tables (cell, weights,

@@ -4,7 +4,12 @@
 (b)  suspended sediment + Exner on the device: the coefficient and facet kernels once per step, the source kernel in front of each of
      the three sediment stages, the Exner kernel and the copy of the bed; batched by swe2d_advance_coupled;
 (c)  the same through the host fallback: a device class without ``sediment_set`` - per step the stepper pulls the flow, evaluates
-     ``HostSediment`` in numpy, pulls the field and uploads the source per stage, and uploads the new bed.
+     ``HostSediment`` in numpy, pulls the field and uploads the source per stage, and uploads the new bed;
+(d)  as (b) with ``use_bedload`` and the default slope corrections, the bedload pass as a launch of its own after the limiter
+     (``fuse_with_sediment = 0``): one more kernel per step (swe_bedload_kernel) and the gather of its contribution planes in the Exner
+     kernel;
+(e)  as (d) with q_b evaluated in the coefficient pass's launch (``fuse_with_sediment``, what FlowSolver2d takes): one launch fewer
+     per step, the friction closures once per node for both - the same bits.
 
     python tools/sedimentbench.py [--nx 707 --ny 707] [--steps 100] [--host-steps 3]
 
@@ -49,6 +54,10 @@ def make_solver(nx, ny, case):
         so.bed_reference_height = Constant(0.025)
         so.morphological_viscosity = Constant(1e-6)
         so.morphological_acceleration_factor = Constant(100.0)
+        so.use_bedload = case in ('d', 'e')
+        if case in ('d', 'e'):
+            from thetis_amd.sediment_model import SedimentModel
+            so.sediment_model_class = type('BenchSedimentModel', (SedimentModel,), {'fuse_bedload': case == 'e'})
     o.set_timestepper_type('SSPRK33')
     for t in (o.swe_timestepper_options, o.tracer_timestepper_options, so.sediment_timestepper_options):
         if hasattr(t, 'use_automatic_timestep'):
@@ -96,7 +105,7 @@ def main():
     ap.add_argument('--host-steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--repeats', type=int, default=3)
-    ap.add_argument('--cases', default='a,b,c')
+    ap.add_argument('--cases', default='a,b,c,d,e')
     args = ap.parse_args()
     res = {'cells': 2*args.nx*args.ny, 'steps': args.steps, 'host_steps': args.host_steps, 'repeats': args.repeats}
     for c in args.cases.split(','):
@@ -105,6 +114,10 @@ def main():
                                       1 if host else args.warmup, 1 if host else args.repeats)
     if 'ms_per_step_a' in res and 'ms_per_step_b' in res:
         res['b_minus_a_ms_per_step'] = res['ms_per_step_b'] - res['ms_per_step_a']
+    if 'ms_per_step_b' in res and 'ms_per_step_d' in res:
+        res['d_minus_b_ms_per_step'] = res['ms_per_step_d'] - res['ms_per_step_b']
+    if 'ms_per_step_d' in res and 'ms_per_step_e' in res:
+        res['e_minus_d_ms_per_step'] = res['ms_per_step_e'] - res['ms_per_step_d']
     if 'ms_per_step_b' in res and 'ms_per_step_c' in res:
         res['c_over_b'] = res['ms_per_step_c']/res['ms_per_step_b']
     print(json.dumps(res))
