@@ -911,6 +911,60 @@ int  swe2d_bedload_read(swe2d_handle *h, double *qbx, double *qby, double *contr
 /* no bedload in the Exner update any more; the planes are freed (and the Exner tables of a handle without a sediment field) */
 int  swe2d_bedload_clear(swe2d_handle *h);
 
+/* ---- Sediment slide in the Exner update (thetis/sediment_model.py:312-354 get_sediment_slide_term, thetis/exner_eq.py:132-149
+ * ExnerSedimentSlideTerm): a diffusion of the bed that switches on in cells steeper than the angle of repose.  The bed is CG-P1, so
+ * the three interior-facet integrals of the reference's term vanish (jump(b) = 0); what remains is  int grad(psi) . (alpha grad(-b)) dx
+ * with residual = -f, alpha the cell-constant scalar below.  With or without a sediment field and a bedload model on the handle.
+ * Per cell k, b_j the bed at the cell's vertices, d psi_j the gradient table of the bedload section, r_k the slide region (1 without
+ * one), dt the handle's step; every comparison a select, no contraction, products and quotients associate from the left:
+ *   bx = (b_0*dpsi_0x + b_1*dpsi_1x) + b_2*dpsi_2x, by likewise;   gx = r_k*bx;  gy = r_k*by
+ *   s2      = gx*gx + gy*gy
+ *   nz      = 1/sqrt(1 + s2)
+ *   sinb    = sqrt(1 - nz*nz)
+ *   tanbeta = sinb/nz
+ *   beta    = asin(sinb)
+ *   d       = tanbeta - tanphi
+ *   qaval   = d > 0 ? ((1 - porosity)*0.5*(L*L)*d)/cos(beta*dt*morfac) : 0          [the reference's cosine, kept verbatim]
+ *   alpha   = sinb > 0 ? -(qaval*(nz*nz))/sinb : 0                                   [the divisor is 1 where sinb == 0]
+ *   c_i     = (A*alpha)*(dpsi_ix*bx + dpsi_iy*by)     [the UNscaled gradient, as in the reference: the region enters the slope test only]
+ * sqrt and the divisions are correctly rounded; asin and cos are the device's math library.  c_0 + c_1 + c_2 = 0 up to rounding (the
+ * hat gradients of a cell add up to zero): the lumped bed volume is conserved, and there is no boundary term.  alpha < 0 makes the
+ * update a diffusion of b.
+ * Exner with slide: the gather adds ns = sum of c_{k,i} over the vertex's list, separately and NOT scaled by fac (the reference does
+ * not multiply this term by morfac/(1 - porosity)):
+ *   b_v = b_v + ((dt*fac)*(num + nb) + dt*ns)/den        (num = 0 without a sediment field, nb = 0 without bedload)
+ *   A handle without slide executes what it executed before.
+ * Counted, not enforced: a cell is FLAGGED when alpha > 0 (the cosine went negative: anti-diffusion) or when
+ *   ((dt*|alpha|)*3)*max_i(dpsi_ix*dpsi_ix + dpsi_iy*dpsi_iy) > 1, a sufficient per-cell bound for the lumped forward-Euler diffusion.
+ *   swe2d_slide_flagged gives the running count of flagged cells over all passes since swe2d_slide_set.
+ * The largest beta of the last pass is kept in one device word as an exact, order-independent maximum (swe2d_slide_max_angle).
+ * Per time step (swe2d_advance_coupled, and swe2d_advance on a handle without a sediment field): flow, tracers, sediment stages,
+ * limiter, bedload, swe2d_slide_update, Exner.  The dataflow kernel declines a handle with slide. */
+typedef struct swe2d_slide_params {
+    double tanphi;           /* tan(max_angle*pi/180), formed by the caller */
+    double length_scale;     /* sed_slide_length_scale L, > 0 */
+    double porosity;
+    double morfac;           /* morphological_acceleration_factor (the cosine's argument) */
+    double fac;              /* morfac/(1 - porosity): read by the Exner update of a handle with neither sediment field nor bedload */
+    double min_depth;        /* likewise: floor of the depth in the Exner update, > 0 */
+    int32_t solve_exner;     /* swe2d_advance_coupled / swe2d_advance update the bed after every step */
+} swe2d_slide_params;
+/* switches the slide on or replaces its parameters and region (allocates the alpha, beta and contribution planes and, where the handle
+ * has none yet, the gradient table and the Exner tables); region_per_cell: [n_cells] or NULL (1 everywhere).  Clears the flagged
+ * count.  SWE2D_ERR_UNSUPPORTED: the cases of swe2d_sediment_set. */
+int  swe2d_slide_set(swe2d_handle *h, const swe2d_slide_params *par, const double *region_per_cell);
+/* alpha, beta, the contribution planes, the maximum and the flagged count from the current bed (asynchronous) */
+int  swe2d_slide_update(swe2d_handle *h);
+/* synchronises; alpha [n_cells], beta [n_cells], contrib nodal [n_cells][3]; any pointer may be NULL */
+int  swe2d_slide_read(swe2d_handle *h, double *alpha, double *beta, double *contrib);
+/* synchronises; the largest beta (radians) of the last swe2d_slide_update, 0 before the first */
+int  swe2d_slide_max_angle(swe2d_handle *h, double *beta_max);
+/* synchronises; cells flagged by the passes since swe2d_slide_set */
+int  swe2d_slide_flagged(swe2d_handle *h, int64_t *n_flagged);
+/* no slide in the Exner update any more; the planes are freed (and the tables nothing else reads): the handle steps as one that
+ * never had it */
+int  swe2d_slide_clear(swe2d_handle *h);
+
 /* ---- Section transports (csrc/swe2d_sections.hip; thetis_amd/sections.py): volume and tracer flux through lines ----
  * The reference has no 2D counterpart (its TransectCallback is 3D, thetis/callback.py:959).  A section is a list of PIECES; a piece
  * is a straight segment inside one cell (a cut of a polyline, or a boundary facet), handed in with its geometry resolved by the host:

@@ -120,6 +120,12 @@ class BedloadParams(ctypes.Structure):
                 ('use_secondary_current', ctypes.c_int32), ('solve_exner', ctypes.c_int32), ('open_markers', ctypes.c_uint32), ('fuse_with_sediment', ctypes.c_int32)]
 
 
+class SlideParams(ctypes.Structure):
+    """include/swe2d.h swe2d_slide_params"""
+    _fields_ = [('tanphi', ctypes.c_double), ('length_scale', ctypes.c_double), ('porosity', ctypes.c_double), ('morfac', ctypes.c_double),
+                ('fac', ctypes.c_double), ('min_depth', ctypes.c_double), ('solve_exner', ctypes.c_int32)]
+
+
 # every symbol include/swe2d.h declares: name -> (restype, argtypes)
 _H = ctypes.c_void_p
 SYMBOLS = {
@@ -275,6 +281,12 @@ SYMBOLS = {
     'swe2d_bedload_update': (ctypes.c_int, [_H]),
     'swe2d_bedload_read': (ctypes.c_int, [_H, _dp, _dp, _dp]),
     'swe2d_bedload_clear': (ctypes.c_int, [_H]),
+    'swe2d_slide_set': (ctypes.c_int, [_H, ctypes.POINTER(SlideParams), _dp]),
+    'swe2d_slide_update': (ctypes.c_int, [_H]),
+    'swe2d_slide_read': (ctypes.c_int, [_H, _dp, _dp, _dp]),
+    'swe2d_slide_max_angle': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_double)]),
+    'swe2d_slide_flagged': (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
+    'swe2d_slide_clear': (ctypes.c_int, [_H]),
     'swe2d_get_bathymetry': (ctypes.c_int, [_H, _dp]),
     'swe2d_set_bathymetry': (ctypes.c_int, [_H, _dp]),
     'swe2d_sections_set': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _ip, _ip, _dp, _dp, ctypes.c_int32, _ip]),

@@ -325,12 +325,13 @@ class _SedimentStepper(object):
         """the bed update after the sediment step (and limiter), the bedload pass on the new flow in front of it"""
         m = self.sediment_model
         contrib = m.update_bedload() if m.use_bedload else None
+        slide = m.update_slide(self.dt) if m.use_sediment_slide else None
         if not self.host_sediment:
             self.device.exner_step()
             return
         E, D, _ = m._terms()
         eta, bath = self._host_fields()
-        new = m.host.exner(E, D, self.device.tracer_get_state(self.tid), eta, bath, self.dt, bedload=contrib)
+        new = m.host.exner(E, D, self.device.tracer_get_state(self.tid), eta, bath, self.dt, bedload=contrib, slide=slide)
         self.device.set_bathymetry(new)
         b = solver.fields.bathymetry_2d
         b._data[...] = new.reshape(b._data.shape)
@@ -364,29 +365,31 @@ class DeviceSedimentForwardEuler(_SedimentStepper, DeviceTracerForwardEuler):
 
 
 class BedloadStepper(object):
-    """The bed of a run with ``use_bedload`` and no sediment field (the reference's meander): after the flow step (and the tracers)
-    the bedload pass and the Exner update, on the device where it has the calls, through ``HostSediment`` and ``set_bathymetry``
-    otherwise."""
+    """The bed of a run with ``use_bedload`` and / or ``use_sediment_slide`` and no sediment field (the reference's meander and its
+    slide test): after the flow step (and the tracers) the bedload pass, the slide pass and the Exner update, on the device where
+    it has the calls, through ``HostSediment`` and ``set_bathymetry`` otherwise."""
 
     def __init__(self, model, device, dt):
         self.sediment_model, self.device, self.dt = model, device, dt
-        self.host_sediment = not hasattr(device, 'bedload_set')
+        need = (['bedload_set'] if model.use_bedload else []) + (['slide_set'] if model.use_sediment_slide else [])
+        self.host_sediment = not all(hasattr(device, n) for n in need)
         if not self.host_sediment:
             model.bind_bedload_device(device)
         elif not hasattr(device, 'set_bathymetry'):
-            raise NotImplementedError('sediment_model_options: a device class without the bedload pass must give set_bathymetry for '
-                                      'the host evaluation')
+            raise NotImplementedError('sediment_model_options: a device class without the bedload and slide passes must give '
+                                      'set_bathymetry for the host evaluation')
 
     def set_dt(self, dt):
         self.dt = dt
 
     def exner_step(self, solver):
         m = self.sediment_model
-        contrib = m.update_bedload()
+        contrib = m.update_bedload() if m.use_bedload else None
+        slide = m.update_slide(self.dt) if m.use_sediment_slide else None
         if not self.host_sediment:
             self.device.exner_step()
             return
-        new = m.host.exner(None, None, None, m.elev.cell_node_values(), m._bathymetry(), self.dt, bedload=contrib)
+        new = m.host.exner(None, None, None, m.elev.cell_node_values(), m._bathymetry(), self.dt, bedload=contrib, slide=slide)
         self.device.set_bathymetry(new)
         b = solver.fields.bathymetry_2d
         b._data[...] = new.reshape(b._data.shape)
@@ -523,11 +526,15 @@ class GeneralCoupledTimeIntegrator2D(TimeIntegratorBase):
             host = host or (self.bed is not None and self.bed.host_sediment)
             if self.bed is not None:
                 self.bed.sediment_model._qb = None
+                if self.bed.sediment_model.on_device:
+                    self.bed.sediment_model._slide = None
             self.solver._bed_device_ahead = not host            # (the host fallback wrote fields.bathymetry_2d itself)
             for ts in self.tracers.values():
                 if getattr(ts, 'sediment_model', None) is not None:
                     ts.sediment_model._planes = None
                     ts.sediment_model._qb = None
+                    if ts.sediment_model.on_device:
+                        ts.sediment_model._slide = None
 
     def diagnostics(self):
         return self.swe.diagnostics()

@@ -921,11 +921,12 @@ int swe2d_advance(swe2d_handle *hh, int n_steps)
     if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance");
     // the dataflow kernel, the three-stage kernel, the fused stage pair + stage 3 or three stage launches: the same bits (swe2d_plan.hip)
-    if (!(h->bed.on && !h->sed.on)) return step_swe(h, kAdvance, n_steps);
-    // a flow-only handle with bedload: the bedload pass and the bed update behind every step, as swe2d_advance_coupled orders them
+    if (!((h->bed.on || h->slide.on) && !h->sed.on)) return step_swe(h, kAdvance, n_steps);
+    // a flow-only handle with bedload or slide: their passes and the bed update behind every step, as swe2d_advance_coupled orders them
     for (int it = 0; it < n_steps; it++) {
         if (int rc = step_swe(h, kAdvance, 1)) return rc;
-        if (int rc = bedload_update_launch(h)) return rc;
+        if (h->bed.on) { if (int rc = bedload_update_launch(h)) return rc; }
+        if (h->slide.on) { if (int rc = slide_update_launch(h)) return rc; }
         if (exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
     }
     return SWE2D_OK;

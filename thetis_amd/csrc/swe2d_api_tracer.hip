@@ -617,11 +617,13 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
             if (use_limiter) { int rc = limiter_apply(h, id, h->n_cells, fuse_mean); if (rc) return rc; }
             // (fused: this step's sediment update wrote q_b already, from the flow and the bed that are still there)
             if (id == sed && h->bed.on && !bedload_fused(h)) { if (int rc = bedload_update_launch(h)) return rc; }
+            if (id == sed && h->slide.on) { if (int rc = slide_update_launch(h)) return rc; }
             if (id == sed && exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
         }
-        // bedload without a sediment field: the pass on the new flow, then the bed
-        if (sed < 0 && h->bed.on) {
-            if (int rc = bedload_update_launch(h)) return rc;
+        // bedload and / or slide without a sediment field: the passes on the new flow, then the bed
+        if (sed < 0 && (h->bed.on || h->slide.on)) {
+            if (h->bed.on) { if (int rc = bedload_update_launch(h)) return rc; }
+            if (h->slide.on) { if (int rc = slide_update_launch(h)) return rc; }
             if (exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
         }
     }

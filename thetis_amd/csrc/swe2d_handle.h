@@ -261,6 +261,15 @@ struct Handle {
         double *grad = nullptr;                         // d psi_i/dx [3][S] | d psi_i/dy [3][S], built on the host
     };
     Bedload bed;
+    // sediment slide in the Exner update (swe2d_sediment.hip); shares the Exner tables of `sed` and the gradient table of `bed`
+    struct Slide {
+        bool on = false;
+        swe2d_slide_params par{};
+        double *planes = nullptr;                       // alpha [S] | beta [S] | contribution [3][S] (swe2d_slide_update)
+        double *region = nullptr;                       // [n_cells] slide region per cell; null: 1 everywhere
+        unsigned long long *words = nullptr;            // [0] bits of the largest beta of the last pass, [1] flagged cells since set
+    };
+    Slide slide;
     int tracer_use_lf = 0;
     double tracer_lf_factor = 1.0, tracer_vel_factor = 1.0;
     std::vector<int> host_cells;                 // [n][3] vertex ids as given (limiter default topology)
@@ -513,10 +522,11 @@ int sediment_source_launch(Handle *h, int in, int c0, int c1);   // in front of 
 int sediment_update_launch(Handle *h);                  // E, D, equilibrium from buffer A + the 'equilibrium' facets of the value table
 int exner_launch(Handle *h);                            // one bed update from the sediment tracer's buffer A and / or the bedload planes
 int bedload_update_launch(Handle *h);                   // q_b and its contribution planes from buffer A and the current bed
+int slide_update_launch(Handle *h);                     // alpha, beta and the slide's contribution planes from the current bed
 bool bedload_fused(const Handle *h);                    // sediment_update_launch writes them too (one launch for both closures)
 inline bool exner_steps(const Handle *h)                // the bed moves after every step of swe2d_advance_coupled / swe2d_advance
 {
-    return (h->sed.on && h->sed.par.solve_exner) || (h->bed.on && h->bed.par.solve_exner);
+    return (h->sed.on && h->sed.par.solve_exner) || (h->bed.on && h->bed.par.solve_exner) || (h->slide.on && h->slide.par.solve_exner);
 }
 void sediment_free(Handle *h);                          // (swe2d_destroy)
 // ---- section transports (swe2d_sections.hip): frees the piece tables and the rows (swe2d_destroy)

@@ -21,6 +21,7 @@ unsigned step_kernels(const Handle *h)
     if (h->atm.n_t > 0) k = 0;                               // atmospheric record: the fields change per stage, a fused launch reads them once
     if (h->sed.on && h->sed.par.solve_exner) k &= ~kFlow;   // Exner: the bed moves after every step, the dataflow kernel batches steps
     if (h->bed.on) k &= ~kFlow;                              // bedload: a pass after every step, and with it the bed moves
+    if (h->slide.on) k &= ~kFlow;                            // sediment slide: likewise
     if (h->opt[SWE2D_OPT_BND_INLINE] == 0) k = 0;            // the epilogue variant was asked for: stage kernels only
     if (h->h_nbr.empty()) k &= ~(kPair | kTriple);           // the tiles are cut from the host copy of the neighbour codes
     if (!h->flow_flag || !h->flow_ex) k &= ~kFlow;           // the dataflow kernel's tables (flow_build)

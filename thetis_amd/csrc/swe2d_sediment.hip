@@ -20,6 +20,13 @@
 //                               gradients of the bed and of the free surface; then the cell's three contributions to the divergence of q_b
 //                               tested with the vertex hat functions, boundary integral of the open facets included.  Written: six q_b
 //                               planes and three contribution planes, which the Exner gather adds up per vertex in list order.
+// swe_slide_kernel           - with the sediment slide (swe2d_slide_set), once per time step after the bedload pass, one lane per cell:
+//                               the slope of the bed from the cell's three vertex beds and the gradient table, the reference's diffusion
+//                               coefficient alpha where the slope exceeds the angle of repose (include/swe2d.h has the formulas), and the
+//                               cell's three contributions A*alpha*(grad psi_i . grad b).  Written: the alpha and beta planes and three
+//                               contribution planes, which the Exner gather adds up per vertex as a sum of its own.  One asin and one cos
+//                               from the device's math library; the largest beta of the pass and the count of flagged cells go to two
+//                               device words, one atomic each per wave that has something to report.
 // The last three and the contribution planes are + - * / in a fixed order without contraction: thetis_amd/sediment_model.py (HostSediment) gives their bits from the
 // same planes.  All loads and stores of a lane are its own cell's / vertex's; plane accesses are coalesced, the gather is not.
 #include "swe2d_handle.h"
@@ -35,12 +42,14 @@ struct SweSedArgs {
     const int *ent;                             // CSR entries: cell << 2 | local node
     const double *area;                         // [n_cells]
     const double *contrib;                      // Exner with bedload: the contribution planes [3][S]
+    const double *slide;                        // Exner with slide: its contribution planes [3][S]
     unsigned *count;
     size_t stride;
     int begin, end;                             // cell range / list length / vertices
     int nonlinear, conservative;
     unsigned eq_markers;
     double dtf, min_depth;                      // Exner: dt*fac, the floor of the depth
+    double dt;                                  // Exner with slide: the step itself (the slide is not scaled by fac)
     swe2d_sediment_params par;
 };
 
@@ -289,9 +298,87 @@ __global__ void __launch_bounds__(256) swe_bedload_kernel(SweBedArgs a)
     }
 }
 
-// SED: the net erosion of the sediment field; BED: the bedload contribution planes (a.contrib).  <true, false> is the update of a handle
-// without bedload, operation by operation what it was before there was one.
-template <bool SED, bool BED>
+struct SweSlideArgs {
+    const int *cv;
+    const double *vh;
+    const double *grad;                         // d psi/dx [3][S] | d psi/dy [3][S]
+    const double *area;
+    const double *region;                       // [n_cells] or null
+    double *planes;                             // alpha [S] | beta [S] | contribution [3][S]
+    unsigned long long *words;                  // [0] bits of the largest beta, [1] flagged cells
+    size_t stride;
+    int n_cells;
+    double dt;
+    swe2d_slide_params par;
+};
+
+// beta >= 0, so the bit pattern of the double orders as the unsigned integer does: the maximum is exact whatever the order of arrival.
+// Lanes past the last cell take part in the wave's reductions with beta = 0 and no flag; they load and store nothing.
+__global__ void __launch_bounds__(256) swe_slide_kernel(SweSlideArgs a)
+{
+#pragma clang fp contract(off)
+    const int k = blockIdx.x*256 + threadIdx.x;
+    const bool in = k < a.n_cells;
+    const size_t S = a.stride;
+    const unsigned k8 = (unsigned)k*8u, k4 = (unsigned)k*4u, S8 = (unsigned)S*8u, S4 = (unsigned)S*4u;
+    double beta = 0.0;
+    bool flag = false;
+    if (in) {
+        const swe_rsrc_t rc = swe_rsrc(a.cv), rh = swe_rsrc(a.vh), rgx = swe_rsrc(a.grad), rgy = swe_rsrc(a.grad + 3*S), ra = swe_rsrc(a.area);
+        const swe_rsrc_t oa = swe_rsrc(a.planes), ob = swe_rsrc(a.planes + S), oc = swe_rsrc(a.planes + 2*S);
+        double b[3], gx[3], gy[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            b[i] = swe_ld(rh, (unsigned)swe_ldi(rc, k4, i*S4)*8u, 0u);
+            gx[i] = swe_ld(rgx, k8, i*S8);
+            gy[i] = swe_ld(rgy, k8, i*S8);
+        }
+        const double A = swe_ld(ra, k8, 0u);
+        const double r = a.region ? swe_ld(swe_rsrc(a.region), k8, 0u) : 1.0;
+        const double bx = (b[0]*gx[0] + b[1]*gx[1]) + b[2]*gx[2], by = (b[0]*gy[0] + b[1]*gy[1]) + b[2]*gy[2];
+        const double sx = r*bx, sy = r*by;
+        const double s2 = sx*sx + sy*sy;
+        const double nz = 1.0/sqrt(1.0 + s2);
+        const double sinb = sqrt(1.0 - nz*nz);
+        const double tanbeta = sinb/nz;
+        beta = asin(sinb);
+        const double d = tanbeta - a.par.tanphi;
+        const bool slides = d > 0.0;
+        const double L = a.par.length_scale;
+        const double cs = slides ? cos(beta*a.dt*a.par.morfac) : 1.0;
+        const double qaval = slides ? ((1.0 - a.par.porosity)*0.5*(L*L)*d)/cs : 0.0;
+        const bool steep = sinb > 0.0;
+        const double q = -(qaval*(nz*nz))/(steep ? sinb : 1.0);
+        const double alpha = steep ? q : 0.0;
+        double gmax = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const double g2 = gx[i]*gx[i] + gy[i]*gy[i];
+            gmax = g2 > gmax ? g2 : gmax;
+            swe_st(oc, k8, i*S8, (A*alpha)*(gx[i]*bx + gy[i]*by));
+        }
+        swe_st(oa, k8, 0u, alpha);
+        swe_st(ob, k8, 0u, beta);
+        flag = alpha > 0.0 || ((a.dt*__builtin_fabs(alpha))*3.0)*gmax > 1.0;
+    }
+    // the wave's maximum and its number of flagged cells, then at most one atomic each from its first lane
+    unsigned long long bits = __builtin_bit_cast(unsigned long long, beta);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(bits, off, 64);
+        bits = o > bits ? o : bits;
+    }
+    const unsigned long long votes = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (bits > __hip_atomic_load(&a.words[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&a.words[0], bits);
+        if (votes) atomicAdd(&a.words[1], (unsigned long long)__popcll(votes));
+    }
+}
+
+// SED: the net erosion of the sediment field; BED: the bedload contribution planes (a.contrib); SLIDE: the slide's (a.slide), summed
+// on their own and scaled by dt alone.  <true, false, false>, <true, true, false> and <false, true, false> are the updates of a handle
+// without slide, operation by operation what they were before there was one.
+template <bool SED, bool BED, bool SLIDE>
 __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
 {
 #pragma clang fp contract(off)
@@ -299,12 +386,12 @@ __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
     if (v >= a.end) return;
     const size_t S = a.stride;
     const unsigned S8 = (unsigned)S*8u, S4 = (unsigned)S*4u;
-    const swe_rsrc_t rb = swe_rsrc(a.contrib);
+    const swe_rsrc_t rb = swe_rsrc(a.contrib), rs = swe_rsrc(a.slide);
     const swe_rsrc_t rE = swe_rsrc(a.planes), rD = swe_rsrc(a.planes + 3*S), re = swe_rsrc(a.state + 6*S), rc = swe_rsrc(a.cv),
                      rh = swe_rsrc(a.vh), rt = swe_rsrc(a.tin), rl = swe_rsrc(a.list), rn = swe_rsrc(a.ent), ra = swe_rsrc(a.area);
     const int e0 = swe_ldi(rl, (unsigned)v*4u, 0u), e1 = swe_ldi(rl, (unsigned)v*4u, 4u);
     const double b_old = swe_ld(rh, (unsigned)v*8u, 0u);
-    double num = 0.0, nb = 0.0, den = 0.0, eta_min = 1e300;
+    double num = 0.0, nb = 0.0, ns = 0.0, den = 0.0, eta_min = 1e300;
     for (int e = e0; e < e1; e++) {
         const int ent = swe_ldi(rn, (unsigned)e*4u, 0u);
         const int k = ent >> 2, i = ent & 3;
@@ -327,13 +414,15 @@ __global__ void __launch_bounds__(256) swe_exner_kernel(SweSedArgs a)
         const double A = swe_ld(ra, k8, 0u);
         if (SED) num = num + (A/12.0)*((2.0*ri + rj) + rk);
         if (BED) nb = nb + swe_ld(rb, k8, (unsigned)i*S8);
+        if (SLIDE) ns = ns + swe_ld(rs, k8, (unsigned)i*S8);
         den = den + A/3.0;
         const double eta = swe_ld(re, k8, (unsigned)i*S8);
         eta_min = eta < eta_min ? eta : eta_min;
     }
     double b_new = b_old;
     if (e1 > e0) {
-        const double b = BED ? b_old + (a.dtf*(num + nb))/den : b_old + (a.dtf*num)/den;
+        const double b = SLIDE ? b_old + (a.dtf*(num + nb) + a.dt*ns)/den
+                               : (BED ? b_old + (a.dtf*(num + nb))/den : b_old + (a.dtf*num)/den);
         // the shallowest depth the DG elevation gives at this vertex on the new bed (linear equations: the bed itself)
         const double Hmin = a.nonlinear ? eta_min + b : b;
         if (Hmin >= a.min_depth) b_new = b;
@@ -377,7 +466,7 @@ void sediment_release(Handle *h)
     Handle::Sediment &s = h->sed;
     if (s.planes) (void)hipFree(s.planes);
     Handle::Sediment none;
-    if (h->bed.on) {                                    // the bedload model goes on reading the Exner tables
+    if (h->bed.on || h->slide.on) {                     // the bedload model and the slide go on reading the Exner tables
         none.v_off = s.v_off; none.v_ent = s.v_ent; none.area = s.area; none.vh_new = s.vh_new; none.count = s.count;
     } else {
         sediment_release_tables(h);
@@ -453,15 +542,53 @@ void bedload_release(Handle *h)
 {
     Handle::Bedload &b = h->bed;
     if (b.planes) (void)hipFree(b.planes);
-    if (b.grad) (void)hipFree(b.grad);
-    b = Handle::Bedload();
+    Handle::Bedload none;
+    if (h->slide.on) none.grad = b.grad;                // the slide goes on reading the gradient table
+    else if (b.grad) (void)hipFree(b.grad);
+    b = none;
+}
+
+void slide_release(Handle *h)
+{
+    Handle::Slide &s = h->slide;
+    void *ptrs[] = {s.planes, s.region, s.words};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    s = Handle::Slide();
+    if (!h->bed.on && h->bed.grad) { (void)hipFree(h->bed.grad); h->bed.grad = nullptr; }
+}
+
+// the gradient table of the bedload pass and the slide (kept with the bedload model, built by whichever comes first)
+int gradient_table_build(Handle *h, const char *who)
+{
+    if (h->bed.grad) return SWE2D_OK;
+    const size_t S = h->stride;
+    const int nv = h->n_vertices;
+    std::vector<double> vx(nv), vy(nv), grad;
+    HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
+    bedload_gradients(h, vx.data(), vy.data(), grad);
+    double *g = nullptr;
+    HIP_TRY(h, hipMalloc(&g, 6*S*sizeof(double)));
+    if (hipMemcpy(g, grad.data(), 6*S*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(g);
+        return fail(h, SWE2D_ERR_HIP, (std::string(who) + ": uploading the gradient table failed").c_str());
+    }
+    h->bed.grad = g;
+    return SWE2D_OK;
 }
 
 int exner_check(Handle *h, const char *who)
 {
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
-    if (!h->sed.on && !h->bed.on)
-        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle has neither a sediment model (swe2d_sediment_set) nor a bedload model (swe2d_bedload_set)");
+    if (!h->sed.on && !h->bed.on && !h->slide.on)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle has neither a sediment model (swe2d_sediment_set) nor a bedload model (swe2d_bedload_set) nor a slide (swe2d_slide_set)");
+    return SWE2D_OK;
+}
+
+int slide_check(Handle *h, const char *who)
+{
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (!h->slide.on) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle has no sediment slide (swe2d_slide_set)");
     return SWE2D_OK;
 }
 
@@ -523,21 +650,47 @@ int swe2d_impl::exner_launch(Handle *h)
     a.out = s.vh_new;
     a.count = s.count;
     a.begin = 0; a.end = h->n_vertices;
-    // (a handle without a sediment field takes the factor and the floor from the bedload parameters)
-    a.dtf = h->par.dt*(s.on ? s.par.fac : h->bed.par.fac);
-    a.min_depth = s.on ? s.par.min_depth : h->bed.par.min_depth;
+    // (a handle without a sediment field takes the factor and the floor from the bedload parameters, one with the slide alone from its)
+    a.dtf = h->par.dt*(s.on ? s.par.fac : (h->bed.on ? h->bed.par.fac : h->slide.par.fac));
+    a.min_depth = s.on ? s.par.min_depth : (h->bed.on ? h->bed.par.min_depth : h->slide.par.min_depth);
     a.contrib = h->bed.on ? h->bed.planes + 6*h->stride : nullptr;
+    a.slide = h->slide.on ? h->slide.planes + 2*h->stride : nullptr;
+    a.dt = h->par.dt;
     SWE_CHK_SYNC(h->stream);
     const dim3 grid(grid_for(h->n_vertices)), block(256);
-    if (s.on && h->bed.on) hipLaunchKernelGGL((swe_exner_kernel<true, true>), grid, block, 0, h->stream, a);
-    else if (s.on) hipLaunchKernelGGL((swe_exner_kernel<true, false>), grid, block, 0, h->stream, a);
-    else hipLaunchKernelGGL((swe_exner_kernel<false, true>), grid, block, 0, h->stream, a);
+    switch ((s.on ? 1 : 0) | (h->bed.on ? 2 : 0) | (h->slide.on ? 4 : 0)) {
+    case 1: hipLaunchKernelGGL((swe_exner_kernel<true, false, false>), grid, block, 0, h->stream, a); break;
+    case 2: hipLaunchKernelGGL((swe_exner_kernel<false, true, false>), grid, block, 0, h->stream, a); break;
+    case 3: hipLaunchKernelGGL((swe_exner_kernel<true, true, false>), grid, block, 0, h->stream, a); break;
+    case 4: hipLaunchKernelGGL((swe_exner_kernel<false, false, true>), grid, block, 0, h->stream, a); break;
+    case 5: hipLaunchKernelGGL((swe_exner_kernel<true, false, true>), grid, block, 0, h->stream, a); break;
+    case 6: hipLaunchKernelGGL((swe_exner_kernel<false, true, true>), grid, block, 0, h->stream, a); break;
+    default: hipLaunchKernelGGL((swe_exner_kernel<true, true, true>), grid, block, 0, h->stream, a); break;
+    }
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->vh, s.vh_new, (size_t)h->n_vertices*sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SWE2D_OK;
 }
 
-void swe2d_impl::sediment_free(Handle *h) { bedload_release(h); sediment_release(h); }
+void swe2d_impl::sediment_free(Handle *h) { slide_release(h); bedload_release(h); sediment_release(h); }
+
+int swe2d_impl::slide_update_launch(Handle *h)
+{
+    Handle::Slide &sl = h->slide;
+    SweSlideArgs a{};
+    a.cv = h->cv; a.vh = h->vh;
+    a.grad = h->bed.grad; a.area = h->sed.area; a.region = sl.region;
+    a.planes = sl.planes; a.words = sl.words;
+    a.stride = h->stride;
+    a.n_cells = h->n_cells;
+    a.dt = h->par.dt;
+    a.par = sl.par;
+    HIP_TRY(h, hipMemsetAsync(sl.words, 0, sizeof(unsigned long long), h->stream));      // the maximum is that of this pass
+    SWE_CHK_SYNC(h->stream);
+    hipLaunchKernelGGL(swe_slide_kernel, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return SWE2D_OK;
+}
 
 namespace {
 template <bool COEF>
@@ -736,21 +889,8 @@ int swe2d_bedload_set(swe2d_handle *hh, const swe2d_bedload_params *par)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     Handle::Bedload &b = h->bed;
     const size_t S = h->stride;
-    const int nv = h->n_vertices;
     if (int rc = exner_tables_build(h, "swe2d_bedload_set")) return rc;
-    if (!b.grad) {
-        std::vector<double> vx(nv), vy(nv), grad;
-        HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
-        bedload_gradients(h, vx.data(), vy.data(), grad);
-        double *g = nullptr;
-        HIP_TRY(h, hipMalloc(&g, 6*S*sizeof(double)));
-        if (hipMemcpy(g, grad.data(), 6*S*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(g);
-            return fail(h, SWE2D_ERR_HIP, "swe2d_bedload_set: uploading the gradient table failed");
-        }
-        b.grad = g;
-    }
+    if (int rc = gradient_table_build(h, "swe2d_bedload_set")) return rc;
     if (!b.planes) {
         HIP_TRY(h, hipMalloc(&b.planes, 9*S*sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(b.planes, 0, 9*S*sizeof(double), h->stream));
@@ -793,7 +933,115 @@ int swe2d_bedload_clear(swe2d_handle *hh)
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     bedload_release(h);
-    if (!h->sed.on) sediment_release_tables(h);
+    if (!h->sed.on && !h->slide.on) sediment_release_tables(h);
+    return SWE2D_OK;
+}
+
+int swe2d_slide_set(swe2d_handle *hh, const swe2d_slide_params *par, const double *region_per_cell)
+{
+    Handle *h = H(hh);
+    if (!h || !par) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_slide_set: null argument");
+    if (h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_slide_set: the sediment model runs on triangles only");
+    if (h->n_owned != h->n_cells) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_slide_set: the sediment model is not available on partitions");
+    if (h->wd) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_slide_set: not with wetting-drying (the depth planes are tied to the bed)");
+    if (par->solve_exner && h->n_farms > 0)
+        return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_slide_set: solve_exner is not available together with tidal turbine farms");
+    if (stream_capturing(h)) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_slide_set inside a stream capture");
+    const double pos[] = {par->tanphi, par->length_scale, par->morfac, par->fac, par->min_depth};
+    for (double x : pos)
+        if (!(x > 0.0) || !std::isfinite(x)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_slide_set: tanphi, length_scale, morfac, fac and min_depth must be positive and finite");
+    if (!(par->porosity >= 0.0) || !(par->porosity < 1.0))
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_slide_set: porosity must lie in [0, 1)");
+    if (region_per_cell)
+        for (int k = 0; k < h->n_cells; k++)
+            if (!std::isfinite(region_per_cell[k])) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_slide_set: the region must be finite");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    Handle::Slide &sl = h->slide;
+    const size_t S = h->stride;
+    if (int rc = exner_tables_build(h, "swe2d_slide_set")) return rc;
+    if (int rc = gradient_table_build(h, "swe2d_slide_set")) return rc;
+    if (!sl.planes) {
+        HIP_TRY(h, hipMalloc(&sl.planes, 5*S*sizeof(double)));
+        HIP_TRY(h, hipMemsetAsync(sl.planes, 0, 5*S*sizeof(double), h->stream));
+    }
+    if (!sl.words) HIP_TRY(h, hipMalloc(&sl.words, 2*sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemsetAsync(sl.words, 0, 2*sizeof(unsigned long long), h->stream));
+    if (region_per_cell) {
+        if (!sl.region) HIP_TRY(h, hipMalloc(&sl.region, (size_t)h->n_cells*sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(sl.region, region_per_cell, (size_t)h->n_cells*sizeof(double), hipMemcpyHostToDevice, h->stream));
+    } else if (sl.region) {
+        HIP_TRY(h, hipFree(sl.region));
+        sl.region = nullptr;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    sl.par = *par;
+    sl.on = true;
+    return SWE2D_OK;
+}
+
+int swe2d_slide_update(swe2d_handle *hh)
+{
+    Handle *h = H(hh);
+    if (int rc = slide_check(h, "swe2d_slide_update")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return slide_update_launch(h);
+}
+
+int swe2d_slide_read(swe2d_handle *hh, double *alpha, double *beta, double *contrib)
+{
+    Handle *h = H(hh);
+    if (int rc = slide_check(h, "swe2d_slide_read")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t S = h->stride;
+    double *cell[2] = {alpha, beta};
+    for (int q = 0; q < 2; q++)
+        if (cell[q]) HIP_TRY(h, hipMemcpyAsync(cell[q], h->slide.planes + q*S, (size_t)h->n_cells*sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (contrib) {
+        hipLaunchKernelGGL(swe_planes_to_nodal, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream,
+                           h->slide.planes + 2*S, h->stage_eta, h->stride, h->n_cells, 3);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(contrib, h->stage_eta, (size_t)3*h->n_cells*sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SWE2D_OK;
+}
+
+int swe2d_slide_max_angle(swe2d_handle *hh, double *beta_max)
+{
+    Handle *h = H(hh);
+    if (int rc = slide_check(h, "swe2d_slide_max_angle")) return rc;
+    if (!beta_max) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    unsigned long long bits = 0;
+    HIP_TRY(h, hipMemcpyAsync(&bits, h->slide.words, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::memcpy(beta_max, &bits, sizeof(double));
+    return SWE2D_OK;
+}
+
+int swe2d_slide_flagged(swe2d_handle *hh, int64_t *n_flagged)
+{
+    Handle *h = H(hh);
+    if (int rc = slide_check(h, "swe2d_slide_flagged")) return rc;
+    if (!n_flagged) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    unsigned long long c = 0;
+    HIP_TRY(h, hipMemcpyAsync(&c, h->slide.words + 1, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *n_flagged = (int64_t)c;
+    return SWE2D_OK;
+}
+
+int swe2d_slide_clear(swe2d_handle *hh)
+{
+    Handle *h = H(hh);
+    if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (!h->slide.on) return SWE2D_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    slide_release(h);
+    if (!h->sed.on && !h->bed.on) sediment_release_tables(h);
     return SWE2D_OK;
 }
 

@@ -1068,6 +1068,43 @@ class Swe2dDevice(object):
     def bedload_clear(self):
         self._ck(self.lib.swe2d_bedload_clear(self.h))
 
+    # -- sediment slide in the Exner update (sediment_model.slide_device_parameters)
+    def slide_set(self, params, region=None):
+        """switches the slide on; ``params``: the fields of ``_lib.SlideParams`` as a dict; ``region``: (N,) per cell in the caller's
+        numbering, or None (1 everywhere)"""
+        p = _lib.SlideParams()
+        for name, ctype in _lib.SlideParams._fields_:
+            setattr(p, name, (int if ctype is ctypes.c_int32 else float)(params[name]))
+        r = None
+        if region is not None:
+            r = np.asarray(region, dtype=np.float64).reshape(self.n_cells)
+            r = np.ascontiguousarray(r[self.perm] if self.perm is not None else r)
+        self._ck(self.lib.swe2d_slide_set(self.h, ctypes.byref(p), None if r is None else _ptr(r)))
+
+    def slide_update(self):
+        """alpha, beta and the slide's contributions to the Exner update from the current bed"""
+        self._ck(self.lib.swe2d_slide_update(self.h))
+
+    def slide_read(self):
+        """(alpha (N,), beta (N,), contributions (N, 3))"""
+        alpha, beta, contrib = np.empty(self.n_cells), np.empty(self.n_cells), np.empty((self.n_cells, self.npc))
+        self._ck(self.lib.swe2d_slide_read(self.h, _ptr(alpha), _ptr(beta), _ptr(contrib)))
+        return self._nodal_out(alpha), self._nodal_out(beta), self._nodal_out(contrib)
+
+    def slide_max_angle(self):
+        """the largest beta (radians) of the last pass: one double from the device"""
+        b = ctypes.c_double(0.0)
+        self._ck(self.lib.swe2d_slide_max_angle(self.h, ctypes.byref(b)))
+        return b.value
+
+    def slide_flagged(self):
+        n = ctypes.c_int64(0)
+        self._ck(self.lib.swe2d_slide_flagged(self.h, ctypes.byref(n)))
+        return n.value
+
+    def slide_clear(self):
+        self._ck(self.lib.swe2d_slide_clear(self.h))
+
     def exner_skipped(self):
         n = ctypes.c_int64(0)
         self._ck(self.lib.swe2d_exner_skipped(self.h, ctypes.byref(n)))

@@ -16,7 +16,8 @@ from .log import print_output
 from .options import Constant
 
 __all__ = ['SedimentModel', 'SedimentEquation2D', 'HostSediment', 'sediment_constants', 'closures', 'check_sediment_options', 'device_parameters',
-           'bedload_constants', 'bedload_closures', 'bedload_device_parameters', 'open_bedload_markers', 'EXNER_MIN_DEPTH']
+           'bedload_constants', 'bedload_closures', 'bedload_device_parameters', 'open_bedload_markers', 'slide_constants',
+           'slide_device_parameters', 'EXNER_MIN_DEPTH']
 
 EXNER_MIN_DEPTH = 1e-3       # a vertex whose depth an Exner update would take below this keeps its bed (and is counted)
 
@@ -163,6 +164,21 @@ def bedload_device_parameters(b, solve_exner=True, min_depth=EXNER_MIN_DEPTH, fu
     return p
 
 
+def slide_constants(c, max_angle=32.0, length_scale=0.0, porosity=0.4, morfac=1.0):
+    """``sediment_constants`` (or ``bedload_constants``) plus what the sediment slide reads (sediment_model.py:312-354): the tangent of
+    the angle of repose ``max_angle`` (degrees), the length scale L, the porosity and the morphological factor of the cosine"""
+    s = dict(c)
+    s.update(tanphi=float(np.tan(float(max_angle)*np.pi/180)), slide_length_scale=float(length_scale), porosity=float(porosity),
+             morfac=float(morfac))
+    return s
+
+
+def slide_device_parameters(s, solve_exner=True, min_depth=EXNER_MIN_DEPTH):
+    """``slide_constants`` -> the fields of include/swe2d.h swe2d_slide_params"""
+    return dict(tanphi=s['tanphi'], length_scale=s['slide_length_scale'], porosity=s['porosity'], morfac=s['morfac'], fac=s['fac'],
+                min_depth=float(min_depth), solve_exner=int(bool(solve_exner)))
+
+
 def _is_zero(v):
     """``float(v) == 0.0`` of the reference's rule; a Function, a tidal forcing or anything without a float() counts as non-zero"""
     try:
@@ -297,10 +313,57 @@ class HostSediment(object):
                 c[b] = np.where(is_open, c[b] + tb, c[b])
         return np.stack(c, axis=1)
 
-    def exner(self, E, D, S, eta, bath, dt, bedload=None):
+    def slide_contributions(self, alpha, bath):
+        """(N, 3): what each cell adds at its three nodes to the slide term  int alpha grad(psi) . grad(b) dx  of the Exner update,
+        from the cell-constant ``alpha`` (N,) and the vertex bathymetry: (A*alpha)*(grad psi_i . grad b), the unscaled gradient"""
+        alpha = np.asarray(alpha, dtype=np.float64)
+        bx, by = self.gradient(np.asarray(bath, dtype=np.float64)[self.cells])
+        A, gx, gy = self.area, self.grad_x, self.grad_y
+        return np.stack([(A*alpha)*(gx[:, i]*bx + gy[:, i]*by) for i in range(3)], axis=1)
+
+    def slide(self, bath, dt, region=None, constants=None):
+        """the sediment slide on the vertex bathymetry ``bath`` with the step ``dt``: ``(alpha, beta, contrib, flagged)`` - the
+        cell-constant diffusion coefficient (N,), the slope angle in radians (N,), the (N, 3) contributions to the Exner update and the
+        number of flagged cells (alpha > 0, or dt above the per-cell bound of the explicit update).  ``region``: (N,) per cell or
+        None; ``constants``: ``slide_constants`` (default: this object's).  Operation by operation what swe_slide_kernel does
+        (include/swe2d.h has the formulas); asin and cos are numpy's."""
+        s = self.c if constants is None else constants
+        tanphi, L, porosity, morfac = s['tanphi'], s['slide_length_scale'], s['porosity'], s['morfac']
+        bx, by = self.gradient(np.asarray(bath, dtype=np.float64)[self.cells])
+        r = 1.0 if region is None else np.asarray(region, dtype=np.float64).reshape(bx.shape)
+        sx, sy = r*bx, r*by
+        s2 = sx*sx + sy*sy
+        nz = 1.0/np.sqrt(1.0 + s2)
+        sinb = np.sqrt(1.0 - nz*nz)
+        tanbeta = sinb/nz
+        beta = np.arcsin(sinb)
+        d = tanbeta - tanphi
+        slides = d > 0.0
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            cs = np.where(slides, np.cos(beta*dt*morfac), 1.0)
+            qaval = np.where(slides, ((1.0 - porosity)*0.5*(L*L)*d)/cs, 0.0)
+            steep = sinb > 0.0
+            alpha = np.where(steep, -(qaval*(nz*nz))/np.where(steep, sinb, 1.0), 0.0)
+            contrib = self.slide_contributions(alpha, bath)
+        return alpha, beta, contrib, int(self.slide_flags(alpha, dt).sum())
+
+    def slide_flags(self, alpha, dt):
+        """(N,) bool: the cells a slide pass with this ``alpha`` flags - alpha > 0 (anti-diffusion), or
+        dt*|alpha|*3*max_i |grad psi_i|^2 > 1, a sufficient per-cell bound for the lumped forward-Euler diffusion"""
+        alpha = np.asarray(alpha, dtype=np.float64)
+        gx, gy = self.grad_x, self.grad_y
+        gmax = np.zeros_like(alpha)
+        for i in range(3):
+            g2 = gx[:, i]*gx[:, i] + gy[:, i]*gy[:, i]
+            gmax = np.where(g2 > gmax, g2, gmax)
+        with np.errstate(invalid='ignore', over='ignore'):
+            return (alpha > 0.0) | (((dt*np.abs(alpha))*3.0)*gmax > 1.0)
+
+    def exner(self, E, D, S, eta, bath, dt, bedload=None, slide=None):
         """one bed update: the new vertex bathymetry (vertices whose depth would fall below the floor keep theirs).  ``bedload``:
         the (N, 3) contributions of ``bedload_contributions``, gathered separately and added to the numerator; ``E`` = None: no
-        sediment field (bedload only)"""
+        sediment field (bedload only).  ``slide``: the (N, 3) contributions of ``slide``, gathered separately and scaled by ``dt``
+        alone: b + ((dt*fac)*(num + nb) + dt*ns)/den"""
         bath = np.asarray(bath, dtype=np.float64)
         r = self.net_erosion(E, D, S, eta, bath) if E is not None else np.zeros(self.cells.shape)
         dtf = dt*self.c['fac']
@@ -317,9 +380,14 @@ class HostSediment(object):
         eta_min = np.full(self.n_vertices, 1e300)
         np.minimum.at(eta_min, vert, eta[k, i])
         used = den > 0.0
+        nb = np.zeros(self.n_vertices)
         if bedload is not None:
-            nb = np.zeros(self.n_vertices)
             np.add.at(nb, vert, np.asarray(bedload, dtype=np.float64)[k, i])
+        if slide is not None:
+            ns = np.zeros(self.n_vertices)
+            np.add.at(ns, vert, np.asarray(slide, dtype=np.float64)[k, i])
+            b = bath + (dtf*(num + nb) + dt*ns)/np.where(used, den, 1.0)
+        elif bedload is not None:
             b = bath + (dtf*(num + nb))/np.where(used, den, 1.0)
         else:
             b = bath + (dtf*num)/np.where(used, den, 1.0)
@@ -345,9 +413,9 @@ def check_sediment_options(options, mesh2d=None, comm=None, tidal_farms=False):
     (``sediment_constants``).  Called when the equations are built."""
     from .shallowwater_eq import physical_constants
     so = options.sediment_model_options
-    if so.use_sediment_slide:
-        raise NotImplementedError('sediment_model_options.use_sediment_slide is not implemented: this build runs the suspended load '
-                                  'and the bedload transport (the slide is a diffusion of the bed of its own)')
+    if so.use_sediment_slide and not so.solve_exner:
+        raise NotImplementedError('sediment_model_options.use_sediment_slide without solve_exner is not implemented: the slide enters '
+                                  'the bed update only, and this build refuses an option it would ignore')
     if so.use_bedload and not so.solve_exner:
         raise NotImplementedError('sediment_model_options.use_bedload without solve_exner is not implemented: the bedload transport '
                                   'enters the bed update only, and this build refuses an option it would ignore')
@@ -357,9 +425,9 @@ def check_sediment_options(options, mesh2d=None, comm=None, tidal_farms=False):
     if so.solve_suspended_sediment and so.use_advective_velocity_correction:
         raise NotImplementedError('sediment_model_options.use_advective_velocity_correction=True is not implemented (the tracer '
                                   'kernels take a scalar velocity factor): set it False')
-    if so.solve_exner and not so.solve_suspended_sediment and not so.use_bedload:
-        raise NotImplementedError('sediment_model_options.solve_exner without solve_suspended_sediment and without use_bedload: the '
-                                  'bed update has no source (set one of the two)')
+    if so.solve_exner and not so.solve_suspended_sediment and not so.use_bedload and not so.use_sediment_slide:
+        raise NotImplementedError('sediment_model_options.solve_exner without solve_suspended_sediment, use_bedload and '
+                                  'use_sediment_slide: the bed update has no source (set one of the three)')
     if options.use_wetting_and_drying:
         raise NotImplementedError('sediment_model_options.solve_suspended_sediment / solve_exner with use_wetting_and_drying is not '
                                   'implemented: the sediment kernels take H = eta + h, not the wetting-drying depth, and the depth '
@@ -396,7 +464,41 @@ def check_sediment_options(options, mesh2d=None, comm=None, tidal_farms=False):
                for name in ('slope_effect_parameter', 'slope_effect_angle_parameter', 'secondary_current_parameter')}
         c = bedload_constants(c, par['slope_effect_parameter'], par['slope_effect_angle_parameter'], par['secondary_current_parameter'],
                               so.use_slope_mag_correction, so.use_angle_correction, so.use_secondary_current)
+    if so.use_sediment_slide:
+        par = {name: _constant_value(name, getattr(so, name)) for name in ('max_angle', 'sed_slide_length_scale')}
+        if not par['sed_slide_length_scale'] > 0.0:
+            raise NotImplementedError('sediment_model_options.use_sediment_slide with sed_slide_length_scale = {:g} is not '
+                                      'implemented: the slide term is proportional to its square, and this build refuses an option '
+                                      'it would ignore (set the length scale to about the mesh size)'.format(par['sed_slide_length_scale']))
+        if not 0.0 < par['max_angle'] < 90.0:
+            raise ValueError('sediment_model_options.max_angle must lie between 0 and 90 degrees')
+        _slide_region(so.slide_region, mesh2d)          # (refused by name here, when the equations are built)
+        c = slide_constants(c, par['max_angle'], par['sed_slide_length_scale'], vals['porosity'],
+                            float(so.morphological_acceleration_factor))
     return c
+
+
+def _slide_region(region, mesh2d):
+    """``slide_region`` as one number per cell: None (no region), a Constant / number, a DG0 Function, or a CG-P1 Function reduced to
+    the mean of its three vertex values; anything else is refused by name"""
+    if region is None:
+        return None
+    if isinstance(region, (int, float, np.floating, Constant)):
+        try:
+            value = float(region)
+        except TypeError:
+            value = None
+        if value is not None:
+            return None if mesh2d is None else np.full(int(np.asarray(mesh2d.cells).shape[0]), value)
+    if isinstance(region, Function) and not region.function_space().vector:
+        fs = region.function_space()
+        if fs.family == 'DG' and fs.degree == 0:
+            return np.array(region.dat.data_ro, dtype=np.float64).reshape(-1)
+        if fs.family == 'CG' and fs.degree == 1:
+            v = np.asarray(region.dat.data_ro, dtype=np.float64).reshape(-1)[np.asarray(fs.mesh().cells)]
+            return ((v[:, 0] + v[:, 1]) + v[:, 2])/3.0
+    raise NotImplementedError('sediment_model_options.slide_region must be None, a Constant, a DG0 Function or a CG-P1 Function on '
+                              'the device path (the slide region is one number per cell)')
 
 
 class SedimentEquation2D(object):
@@ -452,6 +554,9 @@ class SedimentModel(object):
         self._device = None
         self._planes = None
         self._qb = None
+        self._slide = None                      # (alpha, beta) of the last slide pass, per cell
+        self._slide_max = 0.0                   # host path: the largest beta of the last pass, radians
+        self.host_flagged = 0                   # host path: cells the slide passes flagged
         self.bnd_functions = {}                 # the shallow-water boundary dict: which markers the bedload transport leaves through
 
     def device_parameters(self):
@@ -465,6 +570,13 @@ class SedimentModel(object):
         return bedload_device_parameters(self.constants, self.options.sediment_model_options.solve_exner,
                                          fuse_with_sediment=self.fuse_bedload)
 
+    def slide_device_parameters(self):
+        return slide_device_parameters(self.constants, self.options.sediment_model_options.solve_exner)
+
+    def slide_region(self):
+        """the slide region as one number per cell, or None (``_slide_region``)"""
+        return _slide_region(self.options.sediment_model_options.slide_region, self.mesh2d)
+
     def open_markers(self):
         """the mesh markers open to the bedload transport (``open_bedload_markers`` on the shallow-water boundary dict)"""
         return open_bedload_markers(self.bnd_functions, markers=list(self.mesh2d.boundary_markers))
@@ -476,14 +588,22 @@ class SedimentModel(object):
             if self.use_bedload and not hasattr(device, 'bedload_set'):
                 raise NotImplementedError('sediment_model_options.use_bedload: the device class has the sediment passes but not the '
                                           'bedload pass')
+            if self.use_sediment_slide and not hasattr(device, 'slide_set'):
+                raise NotImplementedError('sediment_model_options.use_sediment_slide: the device class has the sediment passes but not '
+                                          'the slide pass')
             device.sediment_set(tracer_id, self.device_parameters())
-            if self.use_bedload:
-                device.bedload_set(self.bedload_device_parameters(), self.open_markers())
+            self._bind_bed_passes(device)
             self._device = device
 
+    def _bind_bed_passes(self, device):
+        if self.use_bedload:
+            device.bedload_set(self.bedload_device_parameters(), self.open_markers())
+        if self.use_sediment_slide:
+            device.slide_set(self.slide_device_parameters(), self.slide_region())
+
     def bind_bedload_device(self, device):
-        """a run without a sediment field: the bedload pass and the bed update run on ``device``"""
-        device.bedload_set(self.bedload_device_parameters(), self.open_markers())
+        """a run without a sediment field: the bedload pass, the slide pass and the bed update run on ``device``"""
+        self._bind_bed_passes(device)
         self._device = device
 
     @property
@@ -528,6 +648,59 @@ class SedimentModel(object):
             lut[m] = s
         nbr = np.where(nbr < 0, -lut[np.where(nbr < 0, -nbr, 0)], nbr)
         return self.host.bedload_contributions(self._qb, nbr, [slot[int(m)] for m in self.open_markers()])
+
+    def update_slide(self, dt):
+        """refresh the slide from the current bed (once per time step, after the bedload pass); returns the contributions to the
+        Exner update on the host path, None on the device (which takes the handle's step)"""
+        self._slide = None
+        if self._device is not None:
+            self._device.slide_update()
+            return None
+        alpha, beta, contrib, flagged = self.host.slide(self._bathymetry(), float(dt), self.slide_region())
+        self._slide = (alpha, beta)
+        self._slide_max = float(beta.max()) if beta.size else 0.0
+        self.host_flagged += flagged
+        return contrib
+
+    def _slide_planes(self):
+        if not self.use_sediment_slide:
+            raise ValueError('sediment_model_options.use_sediment_slide is off')
+        if self._slide is None:
+            if self._device is None:
+                raise ValueError('the slide has not been evaluated yet (assign_initial_conditions does)')
+            alpha, beta, _ = self._device.slide_read()
+            self._slide = (alpha, beta)
+        return self._slide
+
+    def _dg0(self, values, name):
+        from .function import get_functionspace
+        f = Function(get_functionspace(self.mesh2d, 'DG', 0), name=name)
+        f.dat.data[...] = values
+        return f
+
+    def get_sediment_slide_term(self, bathymetry=None):
+        """the cell-constant diffusion coefficient alpha of the last slide pass as a DG0 Function (the reference returns the tensor
+        alpha*I as an expression of ``bathymetry``; the bed is explicit here and the term is that of the current one)"""
+        return self._dg0(self._slide_planes()[0], 'sediment_slide_alpha')
+
+    @property
+    def betaangle(self):
+        """the slope angle of the bed (radians) of the last slide pass, DG0: ``beta.interpolate(sediment_model.betaangle)``"""
+        return self._dg0(self._slide_planes()[1], 'betaangle')
+
+    def max_slope_angle(self):
+        """the largest slope angle of the last slide pass in degrees: one double from the device, not collective"""
+        if not self.use_sediment_slide:
+            raise ValueError('sediment_model_options.use_sediment_slide is off')
+        rad = self._device.slide_max_angle() if self._device is not None else self._slide_max
+        return rad*180.0/np.pi
+
+    def slide_flagged(self):
+        """cells flagged by the slide passes so far: alpha > 0 (the reference's cosine went negative) or a step above the per-cell
+        bound of the explicit update"""
+        if not self.use_sediment_slide:
+            raise ValueError('sediment_model_options.use_sediment_slide is off')
+        return int(self._device.slide_flagged()) if self._device is not None else self.host_flagged
 
     def get_bedload_term(self, bathymetry=None):
         """nodal bedload transport (qbx, qby), each (N, 3), of the last update (``bathymetry``: the reference's argument; the bed is

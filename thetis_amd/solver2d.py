@@ -417,6 +417,8 @@ class FlowSolver2d(object):
         self.timestepper.initialize(self.fields.solution_2d)
         if self.sediment_model is not None and self.sediment_model.use_bedload:
             self.sediment_model.update_bedload()            # q_b of the initial flow (get_bedload_term before the first step)
+        if self.sediment_model is not None and self.sediment_model.use_sediment_slide:
+            self.sediment_model.update_slide(self.dt)       # the slope of the initial bed (betaangle before the first step)
         if self.sediment_model is not None and self.sediment_model.solve_suspended_sediment:
             # the model on the initial flow; without an initial field the sediment starts in equilibrium (solver2d.py:772-783)
             self.timestepper.tracers['sediment_2d'].sediment_update()
@@ -501,6 +503,11 @@ class FlowSolver2d(object):
                       else self.sediment_model.host.n_skipped)
             if n_kept:
                 print_output('exner: {:d} vertex updates skipped (depth below the floor)'.format(n_kept))
+            if self.sediment_model.use_sediment_slide:
+                n_flagged = self.sediment_model.slide_flagged()
+                if n_flagged:
+                    print_output('sediment slide: {:d} cell passes flagged (alpha > 0, or the step above the bound of the explicit '
+                                 'update)'.format(n_flagged))
         sys.stdout.flush()
 
     def iterate(self, update_forcings=None, export_func=None):

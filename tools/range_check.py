@@ -265,7 +265,12 @@ def exercise(only=None):
                 # and the facet codes, writes the six q_b and three contribution planes, which the Exner kernel gathers: every switch
                 # combination next to the sediment field, the launch fused with the coefficient pass, the batch, and a handle with
                 # bedload alone stepped by swe2d_advance.
-                from thetis_amd.sediment_model import bedload_constants, bedload_device_parameters, device_parameters, sediment_constants
+                # Slide (swe_slide_kernel): reads the cell vertices, the bathymetry, the gradient table, the areas and the per-cell region,
+                # writes the alpha and beta planes and three contribution planes, which the Exner kernel gathers as a third sum: next to
+                # sediment + bedload with and without a region, the batch, after the other two are cleared on a handle stepped by
+                # swe2d_advance (swe_exner_kernel<false, false, true>), and with bedload alone.
+                from thetis_amd.sediment_model import (bedload_constants, bedload_device_parameters, device_parameters,
+                                                       sediment_constants, slide_constants, slide_device_parameters)
                 cs = sediment_constants(160e-6, 0.025, 1e-6, morfac=50.0)
                 plain = dev.add_tracer()
                 tid = dev.add_tracer()
@@ -311,13 +316,38 @@ def exercise(only=None):
                             dev.advance_coupled(2, tracer_only=False, use_limiter=True)
                             n_launch += 2*(3 + 6 + 2 + 6 + 3 + 1 + 1)
                         assert np.isfinite(dev.get_bathymetry()).all(), (name, variant)
-                        dev.sediment_clear()                    # bedload alone from here: the Exner tables stay
+                        sl = slide_device_parameters(slide_constants(cs, 1.0, 0.2, 0.4, 50.0), True)
+                        for region in (None, np.where(np.arange(mesh.num_cells) % 3 == 0, 0.0, 1.0)):
+                            dev.slide_set(sl, region)           # sediment + bedload + slide: swe_exner_kernel<true, true, true>
+                            dev.slide_update()
+                            dev.exner_step()
+                            dev.advance_coupled(2, tracer_only=False, use_limiter=True)
+                            n_launch += 2 + 2*(3 + 6 + 2 + 6 + 3 + 1 + 1 + 1)
+                            assert all(np.isfinite(a).all() for a in dev.slide_read()), (name, variant)
+                            dev.slide_max_angle(), dev.slide_flagged()
+                        dev.bedload_clear()                     # sediment + slide: <true, false, true>
+                        dev.slide_update()
+                        dev.exner_step()
+                        dev.bedload_set(bedload_device_parameters(cb, True), markers[:1])
+                        assert np.isfinite(dev.get_bathymetry()).all(), (name, variant)
+                        dev.sediment_clear()                    # bedload and slide from here: the Exner tables stay, <false, true, true>
+                        dev.bedload_update()
+                        dev.slide_update()
+                        dev.exner_step()
+                        dev.advance(2)
+                        dev.slide_clear()                       # bedload alone
                         dev.bedload_update()
                         dev.exner_step()
                         dev.advance(2)
                         assert np.isfinite(dev.get_bathymetry()).all() and not dev.flow_supported(), (name, variant)
-                        dev.bedload_clear()
-                        n_launch += 2 + 2*5
+                        dev.slide_set(sl, None)
+                        dev.bedload_clear()                     # slide alone: the gradient table stays, <false, false, true>
+                        dev.slide_update()
+                        dev.exner_step()
+                        dev.advance(2)
+                        assert np.isfinite(dev.get_bathymetry()).all() and not dev.flow_supported(), (name, variant)
+                        dev.slide_clear()
+                        n_launch += 2 + 3 + 2*6 + 2 + 2*5 + 2 + 2*5
                         n_launch += 2 + 3*2 + 6*2 + 2 + 3 + 1 + 2*(3 + 6 + 2 + 6 + 3 + 1)
             if variant == 'sections':
                 # section transports (csrc/swe2d_sections.hip): swe_section_transport_kernel reads the piece tables (cell, weights,

@@ -9,7 +9,9 @@
      (``fuse_with_sediment = 0``): one more kernel per step (swe_bedload_kernel) and the gather of its contribution planes in the Exner
      kernel;
 (e)  as (d) with q_b evaluated in the coefficient pass's launch (``fuse_with_sediment``, what FlowSolver2d takes): one launch fewer
-     per step, the friction closures once per node for both - the same bits.
+     per step, the friction closures once per node for both - the same bits;
+(f)  as (e) with ``use_sediment_slide`` (length scale 0.2, 22 degrees): one more kernel per step (swe_slide_kernel) in front of the
+     Exner kernel, a 8-byte clear of its maximum word, and the gather of its contribution planes as a third sum.
 
     python tools/sedimentbench.py [--nx 707 --ny 707] [--steps 100] [--host-steps 3]
 
@@ -54,10 +56,14 @@ def make_solver(nx, ny, case):
         so.bed_reference_height = Constant(0.025)
         so.morphological_viscosity = Constant(1e-6)
         so.morphological_acceleration_factor = Constant(100.0)
-        so.use_bedload = case in ('d', 'e')
-        if case in ('d', 'e'):
+        so.use_bedload = case in ('d', 'e', 'f')
+        if case == 'f':
+            so.use_sediment_slide = True
+            so.sed_slide_length_scale = Constant(0.2)
+            so.max_angle = Constant(22)
+        if case in ('d', 'e', 'f'):
             from thetis_amd.sediment_model import SedimentModel
-            so.sediment_model_class = type('BenchSedimentModel', (SedimentModel,), {'fuse_bedload': case == 'e'})
+            so.sediment_model_class = type('BenchSedimentModel', (SedimentModel,), {'fuse_bedload': case in ('e', 'f')})
     o.set_timestepper_type('SSPRK33')
     for t in (o.swe_timestepper_options, o.tracer_timestepper_options, so.sediment_timestepper_options):
         if hasattr(t, 'use_automatic_timestep'):
@@ -105,7 +111,7 @@ def main():
     ap.add_argument('--host-steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--repeats', type=int, default=3)
-    ap.add_argument('--cases', default='a,b,c,d,e')
+    ap.add_argument('--cases', default='a,b,c,d,e,f')
     args = ap.parse_args()
     res = {'cells': 2*args.nx*args.ny, 'steps': args.steps, 'host_steps': args.host_steps, 'repeats': args.repeats}
     for c in args.cases.split(','):
@@ -118,6 +124,8 @@ def main():
         res['d_minus_b_ms_per_step'] = res['ms_per_step_d'] - res['ms_per_step_b']
     if 'ms_per_step_d' in res and 'ms_per_step_e' in res:
         res['e_minus_d_ms_per_step'] = res['ms_per_step_e'] - res['ms_per_step_d']
+    if 'ms_per_step_e' in res and 'ms_per_step_f' in res:
+        res['f_minus_e_ms_per_step'] = res['ms_per_step_f'] - res['ms_per_step_e']
     if 'ms_per_step_b' in res and 'ms_per_step_c' in res:
         res['c_over_b'] = res['ms_per_step_c']/res['ms_per_step_b']
     print(json.dumps(res))
