@@ -469,6 +469,7 @@ int swe2d_create(const swe2d_mesh *mesh, const swe2d_params *params, swe2d_handl
 
     h->h_nbr = nbr;                                    // (host copy of the packed neighbour codes: tile tables of the fused stage pair)
     if (npc == 3) {
+        h->h_cv = cv;
         std::vector<int4> p4((size_t)S, int4{0, 0, 0, 0});
         std::vector<int2> p2((size_t)S, int2{0, 0});
         for (int kk = 0; kk < n; kk++) {

@@ -49,8 +49,10 @@ std::vector<int> tile_records(const TileTable &t, int nfacets)
     return rec;
 }
 
-// allocations and copies: never inside a stream capture (the callers test)
-int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std::vector<int> &counts, const TileTable &t)
+// allocations and copies: never inside a stream capture (the callers test).  slot_data: what goes to ts.slot_src - null: the table's
+// neighbour codes; the three-stage kernel: the slots' decoded byte offsets, two words per slot
+int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std::vector<int> &counts, const TileTable &t,
+                 const std::vector<unsigned> *slot_data = nullptr)
 {
     HIP_TRY(h, hipMalloc(&ts.tile, rec.size()*sizeof(int)));
     HIP_TRY(h, hipMalloc(&ts.counts, counts.size()*sizeof(int)));
@@ -60,6 +62,7 @@ int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std:
     std::vector<int> slots;
     for (size_t i = 0; i + 1 < t.slot_first.size(); i++) { slots.push_back(t.slot_first[i]); slots.push_back(t.slot_first[i + 1] - t.slot_first[i]); }
     std::vector<int> src(t.slot_src);
+    if (slot_data) src.assign(slot_data->begin(), slot_data->end());
     src.push_back(0);
     HIP_TRY(h, hipMalloc(&ts.slots, slots.size()*sizeof(int)));
     HIP_TRY(h, hipMalloc(&ts.slot_src, src.size()*sizeof(int)));
@@ -135,7 +138,10 @@ int fuse123_build(Handle *h)
     if (int rc = build_table(h, kTripleTiles, (int)h->fuse3_order.size() == h->n_cells ? h->fuse3_order : h->fuse_order, h->fuse3_start, t)) return rc;
     std::vector<int> counts;                                // int2 {n_inner, n_mid | rot << 16}
     for (size_t i = 0; i < t.n_inner.size(); i++) { counts.push_back(t.n_inner[i]); counts.push_back(t.n_mid[i] | (t.rot[i] << 16)); }
-    return upload_tiles(h, h->fuse3, tile_records(t, 3), counts, t);
+    // the lanes' and the slots' records, decoded here once per table (swe2d_tiles.h: build_lane_records): the kernel reads no connectivity
+    LaneRecords r;
+    build_lane_records(t, h->h_nbr.data(), h->h_cv.data(), h->stride, SWE_FUSE_WG, 8u*SWE_FUSE3_XG, (unsigned)h->stride*8u, r);
+    return upload_tiles(h, h->fuse3, r.lane, counts, t, &r.slot);
 }
 
 // a whole step: state buffer A (U(0)) -> state buffer B (U(3)), then the two change places
@@ -146,11 +152,10 @@ int launch_fuse123(Handle *h, int cell_end)
     if (!h->fuse3.tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stages: no tile tables (not built inside a stream capture)");
     SweFuse3Args q;
     fill_stage_args(h, q.st, 0, 0, 1, 0.0, 1.0, kBeta[0], 0, h->n_owned);
-    q.st.idxc = h->opt[SWE2D_OPT_COMPACT_IDX] == 0 ? nullptr : h->idxc;
-    q.tile = static_cast<const int2 *>(h->fuse3.tile);
+    q.rec = static_cast<const int4 *>(h->fuse3.tile);
     q.counts = reinterpret_cast<const int2 *>(h->fuse3.counts);
     q.slots = reinterpret_cast<const int2 *>(h->fuse3.slots);
-    q.slot_src = h->fuse3.slot_src;
+    q.slot_off = reinterpret_cast<const uint2 *>(h->fuse3.slot_src);
     q.n_tiles = h->fuse3.n_tiles;
     q.cell_end = cell_end;
     for (int s = 0; s < 3; s++) { q.a0[s] = s ? kAlpha0[s] : 0.0; q.a1[s] = s ? kAlphaIn[s] : 1.0; q.beta[s] = kBeta[s]; }

@@ -230,10 +230,11 @@ static_assert(6*SWE_FUSE3_MAX_OUT <= 9*SWE_FUSE_WG, "the staging area must fit P
 
 struct SweFuse3Args {
     SweStageArgs st;          // uin = U(0) (state buffer A); geometry, connectivity, boundary tables; dt, g, sigma_lf
-    const int2 *tile;         // [n_tiles][256]: as SweFuseArgs::tile (lane of the neighbour in the tile, or bit 9 + staging slot)
+    const int4 *rec;          // [n_tiles][2][256]: the lane records, decoded on the host (swe2d_tiles.h: build_lane_records) - {cell or -1, the
+                              //  three tr words of swe_flow_rhs_facets in bytes}, {8*vertex id x 3, bmarkers}
     const int2 *counts;       // [n_tiles]: {n_inner, n_mid | rot << 16}: roles 0 .. n_inner-1 interior, .. n_mid-1 ring 1; role r on lane (r + 64 rot) & 255
-    const int2 *slots;        // [n_tiles]: {first entry of the tile in slot_src, number of staging slots}
-    const int *slot_src;      // per staging slot the neighbour code of the facet that reads it: (cell << 2) | the cell's facet (swe2d_tiles.h)
+    const int2 *slots;        // [n_tiles]: {first entry of the tile in slot_off, number of staging slots}
+    const uint2 *slot_off;    // per staging slot the byte offsets into the state planes of its source's two nodes on the shared facet
     int n_tiles;
     int cell_end;             // stage 3 (the only one that leaves the chip) on cells [0, cell_end): a partition's last stage range
     double a0[3], a1[3], beta[3];   // Shu-Osher weights per stage (swe2d_ssprk33_coefficients)
@@ -249,9 +250,13 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     const int tile = swe_logical_block(blockIdx.x, gridDim.x);
     if (tile >= q.n_tiles) return;                         // padding of the grid to a multiple of 8
     const int lane = (int)threadIdx.x;
-    const int2 tl = q.tile[(size_t)tile*SWE_FUSE_WG + lane];
-    const bool real = tl.x >= 0;
-    const int k = real ? tl.x : 0;
+    // the lane's record (swe2d_tiles.h: build_lane_records): decoded on the host, once per table - nothing here unpacks connectivity,
+    // forms an LDS address or looks at a neighbour code (round 20)
+    const int4 *const rec = q.rec + (size_t)tile*(2*SWE_FUSE_WG) + lane;
+    const int4 ra = rec[0];                                // {cell or -1, tr[0..2]}
+    const int4 rb = rec[SWE_FUSE_WG];                      // {8*vertex 0..2, bmarkers}
+    const bool real = ra.x >= 0;
+    const int k = real ? ra.x : 0;
     const int2 cnt = q.counts[tile];
     const int n_inner = cnt.x, n_mid = cnt.y & 0xffff, rot64 = (cnt.y >> 16) << 6;
     const size_t S = p.stride;
@@ -267,20 +272,18 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     // the prologue waits for four equal shares instead of one or two full waves (224 slots at most: 56 lanes of a wave).
     const int2 sl = q.slots[tile];
     const int slot = ((lane & 63) << 2) | (lane >> 6);
-    int scode = -1;                                        // the slot's source (cell << 2) | facet, fetched before the cell's own chain of loads starts
-    if (slot < sl.y) scode = q.slot_src[sl.x + slot];
+    const bool has_slot = slot < sl.y;
+    uint2 so = {0u, 0u};                                   // the slot's two byte offsets into the state planes, fetched next to the lane's record
+    if (has_slot) so = q.slot_off[sl.x + slot];
 
-    int bmarkers = 0, bkind1 = 0;
+    int bmarkers = rb.w, bkind1 = 0;
     // per facet the BYTE addresses of component 0's two traces (swe_flow_rhs_facets, SWE_TR_BYTES): 16 bits each
-    unsigned tr[3][1];
+    unsigned tr[3][1] = {{(unsigned)ra.y}, {(unsigned)ra.z}, {(unsigned)ra.w}};
     double h[3], nx[3], ny[3], u[3], v[3], e[3];
     double px[3], py[3];
     const swe_rsrc_t gu = swe_rsrc(p.uin), gv = swe_rsrc(p.uin + 3*S), ge = swe_rsrc(p.uin + 6*S);
     if (real) {
-        int nb[3], vid[3];
-        swe_conn_load(p.idxc, p.idx4, p.idx2, k, nb, vid);
-        bmarkers = (nb[0] < 0 ? -nb[0] : 0) | (nb[1] < 0 ? (-nb[1]) << 8 : 0) | (nb[2] < 0 ? (-nb[2]) << 16 : 0);
-        if (bmarkers != 0) {
+        if (bmarkers != 0) {                               // (a look-up, not a record field: swe2d_set_bc changes a marker's kind under a built table)
             const int m1 = (bmarkers & 0xff) ? (bmarkers & 0xff) : ((bmarkers & 0xff00) ? ((bmarkers >> 8) & 0xff) : (bmarkers >> 16));
             bkind1 = m1 < SWE_MAX_MARKERS ? p.bc.kind[m1] : 0;
         }
@@ -290,33 +293,18 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             v[i] = swe_ld(gv, k8, i*S8);
             e[i] = swe_ld(ge, k8, i*S8);
         }
-#pragma unroll
-        for (int f = 0; f < 3; f++) {
-            const int nbf = nb[f];
-            const unsigned w = ((unsigned)tl.y >> (SWE_FUSE_FBITS*f)) & 0x3ffu;
-            const bool outside = (w & 0x200u) != 0u;
-            const unsigned at = w & 0x1ffu;                                   // lane in the tile, or staging slot
-            // the neighbour traverses the shared facet backwards: its node f2 sits on my node f + 1, its node (f2 + 1) % 3 on my node f
-            const int f2 = nbf >= 0 ? (nbf & 3) : f, f2a = f2 == 2 ? 0 : f2 + 1;
-            const unsigned ab = outside ? (unsigned)(8*SWE_FUSE3_XG) + 48u*at : (unsigned)(8*SWE_FUSE_WG*f2) + 8u*at;
-            const unsigned aa = outside ? (unsigned)(8*SWE_FUSE3_XG + 24) + 48u*at : (unsigned)(8*SWE_FUSE_WG*f2a) + 8u*at;
-            tr[f][0] = ab | (aa << 16);
-        }
         const swe_rsrc_t rvx = swe_rsrc(p.vx), rvy = swe_rsrc(p.vy), rvh = swe_rsrc(p.vh);
+        const unsigned v8[3] = {(unsigned)rb.x, (unsigned)rb.y, (unsigned)rb.z};
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            const unsigned v8 = (unsigned)vid[i]*8u;
-            px[i] = swe_ld(rvx, v8, 0);
-            py[i] = swe_ld(rvy, v8, 0);
-            h[i] = swe_ld(rvh, v8, 0);
+            px[i] = swe_ld(rvx, v8[i], 0);
+            py[i] = swe_ld(rvy, v8[i], 0);
+            h[i] = swe_ld(rvh, v8[i], 0);
         }
     }
     double r0[6];
-    if (scode >= 0) {                                      // issued behind the cell's own loads, before anything waits for those
-        const unsigned kn8 = (unsigned)(scode >> 2)*8u;
-        const int g2 = scode & 3;
-        const unsigned ob = kn8 + (g2 == 0 ? 0u : (g2 == 1 ? S8 : 2u*S8));         // node g2: on the reader's node f + 1
-        const unsigned oa = kn8 + (g2 == 0 ? S8 : (g2 == 1 ? 2u*S8 : 0u));         // node (g2 + 1) % 3: on the reader's node f
+    if (has_slot) {                                        // issued behind the cell's own loads, before anything waits for those
+        const unsigned ob = so.x, oa = so.y;               // the source's node on the reader's node f + 1 / on its node f
         r0[0] = swe_ld(gu, ob, 0); r0[1] = swe_ld(gv, ob, 0); r0[2] = swe_ld(ge, ob, 0);
         r0[3] = swe_ld(gu, oa, 0); r0[4] = swe_ld(gv, oa, 0); r0[5] = swe_ld(ge, oa, 0);
     }
@@ -330,7 +318,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
 #pragma unroll
         for (int i = 0; i < 3; i++) { lds[i*SWE_FUSE_WG + lane] = u[i]; lds[(3 + i)*SWE_FUSE_WG + lane] = v[i]; lds[(6 + i)*SWE_FUSE_WG + lane] = e[i]; }
     }
-    if (scode >= 0) {
+    if (has_slot) {
 #pragma unroll
         for (int j = 0; j < 6; j++) lds[SWE_LDSI(SWE_FUSE3_XG + 6*slot + j, SWE_FUSE3_LDS)] = r0[j];
     }
@@ -431,9 +419,11 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
 //  the stages, the velocity traces in registers, bit for bit the stage launches.  Slower at every size: tracer only at 1 M cells 89.7
 //  against 78.0 us per step, at 4 M 424.9 against 391.6 - profiles/r06d_cfgs*.txt, r06e_cfgs_4m.txt, DESIGN_ANNEX.md A8.)
 //
-// (Also measured and not kept: tile records that carry the cell's connectivity - 32 B per lane, two int4 - so that a lane issues its
-//  loads after ONE trip to memory instead of two (tile entry, then the connectivity record): 2-6 % slower at 250 k ... 4 M cells,
-//  the 12 B per cell it adds cost more than the trip it saves - profiles/r06f_fused_sizes.txt against r06b_fused_sizes.txt.)
+// (Round 6, measured and not kept: tile records that carried the cell's PACKED connectivity - 32 B per lane, two int4 - so that a lane
+//  issued its loads after ONE trip to memory instead of two (tile entry, then the connectivity record).  That removed the trip and
+//  nothing else: every lane still unpacked the record and formed its addresses from it, and the table grew by 12 B per cell.  2-6 %
+//  slower at 250 k ... 4 M cells - profiles/r06f_fused_sizes.txt against r06b_fused_sizes.txt.  The lane records of round 20 above
+//  have the same size and hold the DECODED words: the trip and the decode both go.)
 
 // ---- stages 1 and 2 of a step in one launch on QUADRILATERALS (round 6): the triangle kernel's tiles with four facets per cell ------
 // 256 lanes = up to 192 interior cells + their ring of at most 64 (a 16 x 12 tile of a structured mesh: ring 56); the arithmetic is

@@ -99,10 +99,12 @@ extern std::atomic<unsigned long long> g_next_uid;
 
 // the tile tables of one fused kernel on the device (swe2d_api_fuse.hip: upload_tiles / free_tiles); tile == null: not built
 struct TileSet {
-    void *tile = nullptr;                               // [n_tiles][256] records: int2, quadrilaterals int4 (SweFuseArgs / SweFuseQuadArgs / SweFuse3Args)
+    void *tile = nullptr;                               // [n_tiles][256] records: int2, quadrilaterals int4 (SweFuseArgs / SweFuseQuadArgs); two-ring
+                                                        // tiles: [n_tiles][2][256] int4, the decoded lane records (SweFuse3Args::rec)
     int *counts = nullptr;                              // [n_tiles] n_inner; two-ring tiles: int2 {n_inner, n_mid | rot << 16}
     int *slots = nullptr;                               // [n_tiles] int2 {first slot in slot_src, number of staging slots}
-    int *slot_src = nullptr;                            // neighbour code of every staging slot, tile after tile (swe2d_tiles.h)
+    int *slot_src = nullptr;                            // neighbour code of every staging slot, tile after tile (swe2d_tiles.h); two-ring tiles:
+                                                        // uint2 per slot, its decoded byte offsets (SweFuse3Args::slot_off)
     int n_tiles = 0;
     long long ring[2] = {0, 0};                         // cells of ring 1 / ring 2 over all tiles
 };
@@ -154,6 +156,7 @@ struct Handle {
     std::vector<unsigned char> fuse3_start;             // [n_cells] 1 = a two-ring tile must begin at this position of the order; empty: none
     int n_conn_escapes = 0;                             // cells whose record is an escape to the wide ones
     std::vector<int> h_nbr;                             // host copy of the packed neighbour codes [3][S] (triangles; flow_build)
+    std::vector<int> h_cv;                              // host copy of the vertex ids [3][S] (triangles: the lane records of the two-ring tiles)
     // dataflow stage loop (swe2d_flow.h): per-block stage counters, status word {timeouts, first late block + 1}
     unsigned *flow_flag = nullptr, *flow_status = nullptr;
     int4 *flow_xo4 = nullptr;                           // exchange slots of the rim facets (facets between two 64-cell blocks), see SweFlowArgs

@@ -141,4 +141,60 @@ inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *or
     return 0;
 }
 
+// ---- the lane records of the three-stage kernel (swe2d_fuse.h: swe_fuse123_kernel) ---------------------------------------------------
+// Everything a lane of a tile derives from the mesh and the table before its first load of the state, decoded once here instead of in
+// every lane of every step: the kernel reads the words and issues its loads.  Two planes of wg int4 per tile, by physical lane:
+//   lane[((2*tile + 0)*wg + l)*4 ..] = {cell or -1, tr[0], tr[1], tr[2]}: per facet f the BYTE address in LDS of component 0's trace at
+//       the neighbour's node on my node f + 1, | the same on my node f << 16.  The neighbour traverses the shared facet backwards: its
+//       node g sits on my node f + 1, its node (g + 1) % 3 on my node f, g = the low two bits of the neighbour code (a boundary facet:
+//       g = f, and the table's field is the lane itself).  A neighbour in the tile on lane `at`: plane g of the 8-byte planes of wg
+//       lanes, plane_g*8*wg + 8*at; outside, in staging slot `at`: xg_bytes + 48*at and 24 further ([slot][6] doubles);
+//   lane[((2*tile + 1)*wg + l)*4 ..] = {8*vertex 0, 8*vertex 1, 8*vertex 2, bmarkers}: the byte offsets of the cell's vertices in the
+//       coordinate arrays, and 8 bits of marker per boundary facet (marker of facet f << 8 f, 0 for a facet with a neighbour).
+// A padding lane: {-1, 0, 0, 0}, {0, 0, 0, 0}.
+// Per staging slot, slot[2*(slot_first[tile] + s) ..] = {ob, oa}: the byte offsets into the three state planes of one component
+// (plane length s8 bytes) of the slot's source cell at its node g and at its node (g + 1) % 3, source = slot_src = (cell << 2) | g.
+// The arithmetic is the unsigned 32-bit arithmetic the kernel did: the words are the bits it formed.
+struct LaneRecords {
+    std::vector<int> lane;                 // [n_tiles][2][wg] int4
+    std::vector<unsigned> slot;            // [slot_first[n_tiles]] uint2
+};
+
+// nbr, cv: [3][stride] neighbour codes and vertex ids (triangles).  xg_bytes: where the staging area starts in LDS; s8: the byte length
+// of a state plane.
+inline void build_lane_records(const TileTable &t, const int *nbr, const int *cv, size_t stride, int wg, unsigned xg_bytes, unsigned s8,
+                               LaneRecords &r)
+{
+    const size_t n_tiles = t.n_inner.size();
+    r.lane.assign(n_tiles*2*(size_t)wg*4, 0);
+    r.slot.assign(2*t.slot_src.size(), 0u);
+    const unsigned plane = 8u*(unsigned)wg;
+    for (size_t tile = 0; tile < n_tiles; tile++) {
+        for (int l = 0; l < wg; l++) {
+            int *a = &r.lane[((2*tile + 0)*wg + l)*4], *b = &r.lane[((2*tile + 1)*wg + l)*4];
+            const int c = t.cell[tile*wg + l];
+            a[0] = c;
+            if (c < 0) { a[0] = -1; continue; }
+            unsigned bm = 0u;
+            for (int f = 0; f < 3; f++) {
+                const int code = nbr[(size_t)f*stride + c];
+                const unsigned w = t.facet[(tile*wg + l)*3 + f], at = w & 0x1ffu;
+                const unsigned g = code >= 0 ? (unsigned)(code & 3) : (unsigned)f, ga = g == 2u ? 0u : g + 1u;
+                const bool outside = (w & kTileOutside) != 0u;
+                const unsigned ab = outside ? xg_bytes + 48u*at : plane*g + 8u*at;
+                const unsigned aa = outside ? xg_bytes + 24u + 48u*at : plane*ga + 8u*at;
+                a[1 + f] = (int)(ab | (aa << 16));
+                if (code < 0) bm |= (unsigned)(-code) << (8*f);
+                b[f] = (int)((unsigned)cv[(size_t)f*stride + c]*8u);
+            }
+            b[3] = (int)bm;
+        }
+    }
+    for (size_t s = 0; s < t.slot_src.size(); s++) {
+        const unsigned code = (unsigned)t.slot_src[s], kn8 = (code >> 2)*8u, g = code & 3u;
+        r.slot[2*s] = kn8 + (g == 0u ? 0u : (g == 1u ? s8 : 2u*s8));
+        r.slot[2*s + 1] = kn8 + (g == 0u ? s8 : (g == 1u ? 2u*s8 : 0u));
+    }
+}
+
 }  // namespace swe2d_impl
