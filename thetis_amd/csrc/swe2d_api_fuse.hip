@@ -24,7 +24,7 @@ template <bool... B, class F, class... Rest> auto pick_instance(F f, bool b, Res
 // on the physical lane (r + 64*rot) & 255.
 const TileSpec kPairTiles{3, 1, SWE_FUSE_WG, SWE_FUSE_INNER, SWE_FUSE_RING, SWE_FUSE_MAX_OUT, false};
 const TileSpec kQuadPairTiles{4, 1, SWE_FUSE_WG, SWE_QFUSE_INNER, SWE_QFUSE_RING, SWE_QFUSE_MAX_OUT, false};
-const TileSpec kTripleTiles{3, 2, SWE_FUSE_WG, SWE_FUSE_WG, -1, SWE_FUSE3_MAX_OUT, true};
+const TileSpec kTripleTiles{3, 2, SWE_FUSE_WG, SWE_FUSE_WG, -1, SWE_FUSE3_MAX_OUT, true, true};     // (rotated; wall cells on consecutive roles)
 
 int build_table(Handle *h, const TileSpec &spec, const std::vector<int> &order, const std::vector<unsigned char> &start, TileTable &t)
 {

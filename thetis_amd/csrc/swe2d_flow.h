@@ -255,6 +255,8 @@ __device__ __forceinline__ bool swe_flow_arrived(swe_u32x4 g, unsigned need)
 //  SWE_TR_BYTES: in bytes, no shift is left between the word and the DS instruction; SWE_TR_BYTES_INSIDE: in bytes, and the caller
 //  knows that every trace lies in the planes - stages 2 and 3 of the three-stage kernel -, so the components are 3*PLANE and 6*PLANE
 //  doubles on: immediate offsets of the DS instruction, nothing to select and nothing to add)
+// (WAVEB: a boundary facet's flux is zeroed behind a wave-uniform branch, __any(bmarkers != 0) formed here once and handed to
+//  swe_tri_facet; the three-stage kernel only)
 #define SWE_TR_INDEX 0
 #define SWE_TR_BYTES 1
 #define SWE_TR_BYTES_INSIDE 2
@@ -264,13 +266,14 @@ __device__ __forceinline__ bool swe_flow_arrived(swe_u32x4 g, unsigned need)
 #define SWE_LDSB(p_, b_, n_) (*reinterpret_cast<const double *>(reinterpret_cast<const char *>(p_) + (b_)))
 #endif
 template <bool NONLIN, bool LF, bool SRC, int NTR, bool WD = false, int XG = SWE_FLOW_XG, int PLANE = SWE_BLOCK, int NLDS = SWE_FLOW_LDS_DOUBLES,
-          int GEOM = SWE_GEOM_COMPUTE, int TRB = SWE_TR_INDEX>
+          int GEOM = SWE_GEOM_COMPUTE, int TRB = SWE_TR_INDEX, bool WAVEB = false>
 __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k, const double u[3], const double v[3], const double e[3],
                                                     const double h[3], const double *lds, const unsigned tr[3][NTR], int bmarkers,
                                                     const double nx[3], const double ny[3], double twoA, double bu[3], double bv[3],
                                                     double be[3], const double *Dn = nullptr, const double *al = nullptr, double *geo = nullptr)
 {
 #pragma clang fp contract(off)
+    const bool wave_bnd = WAVEB ? __any(bmarkers != 0) != 0 : true;       // wave-uniform: a scalar branch per facet, see swe_tri_facet
 #pragma unroll
     for (int f = 0; f < 3; f++) {
         const int a = f, b = (f + 1) % 3;
@@ -295,9 +298,9 @@ __device__ __forceinline__ void swe_flow_rhs_facets(const SweStageArgs &p, int k
         if constexpr (GEOM == SWE_GEOM_STORED) { Lf = geo[f*PLANE]; rLf = geo[(3 + f)*PLANE]; }
         else swe_tri_facet_len(nx[f], ny[f], Lf, rLf);
         if constexpr (GEOM == SWE_GEOM_KEEP) { geo[f*PLANE] = Lf; geo[(3 + f)*PLANE] = rLf; }
-        swe_tri_facet<NONLIN, LF, WD>(p.g, p.sigma_lf, ((bmarkers >> (8*f)) & 0xff) != 0, u[a], u[b], v[a], v[b], e[a], e[b], h[a], h[b],
-                                      WD ? Dn[a] : 0.0, WD ? Dn[b] : 0.0, WD ? al[a] : 0.0, WD ? al[b] : 0.0, una, unb, vna, vnb, ena, enb,
-                                      nx[f], ny[f], Lf, rLf, bu[a], bu[b], bv[a], bv[b], be[a], be[b]);
+        swe_tri_facet<NONLIN, LF, WD, false, WAVEB>(p.g, p.sigma_lf, ((bmarkers >> (8*f)) & 0xff) != 0, u[a], u[b], v[a], v[b], e[a], e[b], h[a],
+                                                    h[b], WD ? Dn[a] : 0.0, WD ? Dn[b] : 0.0, WD ? al[a] : 0.0, WD ? al[b] : 0.0, una, unb, vna,
+                                                    vnb, ena, enb, nx[f], ny[f], Lf, rLf, bu[a], bu[b], bv[a], bv[b], be[a], be[b], wave_bnd);
     }
     if (SRC) {
         double H[3], gxs[3], gys[3];

@@ -333,7 +333,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         double H[3];
         swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
         swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
-        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1, SWE_TR_BYTES>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1, SWE_TR_BYTES, true>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                      nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             double H[3];
             swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
             swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
-            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23, SWE_TR_BYTES_INSIDE>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+            swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, 9*SWE_FUSE_WG, GEOM23, SWE_TR_BYTES_INSIDE, true>(p, k, u, v, e, h, P1, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                           nullptr, nullptr, G);
             const double a0 = q.a0[s], a1 = q.a1[s];
 #pragma unroll

@@ -5,6 +5,7 @@
 // tiles) ring 2, the facet neighbours of ring 1.  The interior grows cell by cell while the caps of the TileSpec hold - and, where the
 // caller marks positions of the order as tile starts, up to the next mark.  ROLES are numbered [interior in the order added | ring 1 |
 // ring 2], each ring in the order of discovery without the cells that moved inwards later; the rest of the wg lanes is padding.
+// (TileSpec::group_walls: inside each of the three classes the cells with a boundary facet take consecutive roles, see build_tiles.)
 // Per role and facet the table holds a 10-bit field: the lane of the neighbour in the tile (a boundary facet: the lane itself) or,
 // with bit 9 set, the staging slot of a neighbour outside the tile - only facets of the outermost ring lead there, slots are counted
 // per tile in role order.  How the fields are packed into device records is the caller's (swe2d_api_fuse.hip).
@@ -18,6 +19,7 @@
 // the dealing of workgroups over the compute units of an XCD can hand one compute unit tiles of a single residue.  The top two bits of
 // tile x 2^32/phi instead: every arithmetic progression of tile numbers meets the four values equally often.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <string>
 #include <utility>
@@ -39,6 +41,7 @@ struct TileSpec {
     int max_ring1;            // cap of ring 1; < 0: only the total is bounded
     int max_out;              // staging slots: (nfacets - 1) per cell of the outermost ring must fit
     bool rotate;              // rot of tile t = SWE_FUSE3_ROT(t), else 0
+    bool group_walls = false; // the cells with a boundary facet of a tile on consecutive roles, see build_tiles (the three-stage kernel)
 };
 
 struct TileTable {
@@ -107,6 +110,61 @@ inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *or
         for (int want = 2; want <= 3; want++)
             for (int c : touched) if (state[c] == want) cells.push_back(c);
         const int ni = (int)inner.size(), nm = ni + count[2], nt = (int)cells.size();
+        // group_walls: a wave with a wall cell among its lanes runs the boundary pass of swe_tri_finish (once, twice with a corner cell), in
+        // every stage that is active on it - stage 1 on every role, stage 2 below nm, stage 3 below ni.  In the order above the wall cells
+        // of a patch at the wall lie all over its roles, so nearly every wave of the tile pays.  Here the wall cells of each class take
+        // consecutive roles, inside the group and around it the order above.  Where the group sits in its class is chosen so that the
+        // fewest (wave, stage) pairs hold a wall cell - waves are 64 consecutive roles, whatever the rotation: first choice the END of
+        // the interior and the START of each ring (one run across ni, the bound of stage 3), else a place at an end of the class or
+        // against a multiple of 64 that does better (a group that would straddle a wave it need not touch).  A tile without a wall cell
+        // keeps its roles, and so does one - none known - that no such placement serves as well as the order above.  The rings' caps, the
+        // counts and the slots (numbered in role order below) do not look at the order.
+        if (sp.group_walls) {
+            auto wall = [&](int c) { for (int f = 0; f < nf; f++) if (nbr[(size_t)f*stride + c] < 0) return true; return false; };
+            const int bound[4] = {0, ni, nm, nt}, limit[3] = {nt, nm, ni};
+            std::vector<int> walls[3], rest[3];
+            for (int cls = 0; cls < 3; cls++)
+                for (int l = bound[cls]; l < bound[cls + 1]; l++) (wall(cells[l]) ? walls[cls] : rest[cls]).push_back(cells[l]);
+            auto pairs_of = [&](const unsigned char *is_wall) {          // is_wall[role]
+                int pairs = 0;
+                for (int st = 0; st < 3; st++) {
+                    unsigned waves = 0u;
+                    for (int r = 0; r < limit[st]; r++) if (is_wall[r]) waves |= 1u << (r >> 6);
+                    for (; waves; waves &= waves - 1) pairs++;
+                }
+                return pairs;
+            };
+            if (!walls[0].empty() || !walls[1].empty() || !walls[2].empty()) {
+                std::vector<unsigned char> mark((size_t)nt + 1, 0);
+                for (int l = 0; l < nt; l++) mark[l] = wall(cells[l]);
+                int best = pairs_of(mark.data()) + 1, best_off[3] = {-1, -1, -1};     // (+ 1: a tie with the order above goes to the grouping)
+                std::vector<int> cand[3];
+                for (int cls = 0; cls < 3; cls++) {
+                    const int w = (int)walls[cls].size(), room = (int)rest[cls].size();
+                    cand[cls].push_back(cls == 0 ? room : 0);
+                    cand[cls].push_back(cls == 0 ? 0 : room);
+                    for (int edge = 64; edge < wg && w > 0; edge += 64)
+                        for (int o : {edge - bound[cls], edge - w - bound[cls]}) if (o > 0 && o < room) cand[cls].push_back(o);
+                }
+                for (int o0 : cand[0]) for (int o1 : cand[1]) for (int o2 : cand[2]) {
+                    const int off[3] = {o0, o1, o2};
+                    std::fill(mark.begin(), mark.end(), 0);
+                    for (int cls = 0; cls < 3; cls++)
+                        for (int l = 0; l < (int)walls[cls].size(); l++) mark[bound[cls] + off[cls] + l] = 1;
+                    const int pairs = pairs_of(mark.data());
+                    if (pairs < best) { best = pairs; best_off[0] = o0; best_off[1] = o1; best_off[2] = o2; }
+                }
+                if (best_off[0] >= 0) {
+                    std::vector<int> sorted;
+                    for (int cls = 0; cls < 3; cls++) {
+                        sorted.insert(sorted.end(), rest[cls].begin(), rest[cls].begin() + best_off[cls]);
+                        sorted.insert(sorted.end(), walls[cls].begin(), walls[cls].end());
+                        sorted.insert(sorted.end(), rest[cls].begin() + best_off[cls], rest[cls].end());
+                    }
+                    cells.swap(sorted);
+                }
+            }
+        }
         if (nt != count[1] + count[2] + count[3] || ni != count[1] || nt > wg) { err = std::string(who) + "tile bookkeeping"; return 1; }
         const int tile = (int)t.n_inner.size();
         const int rot = sp.rotate ? SWE_FUSE3_ROT(tile) & 3 : 0;
@@ -139,6 +197,31 @@ inline int build_tiles(const int *nbr, size_t stride, int n_cells, const int *or
         for (int c : cells) { state[c] = 0; lane_of[c] = -1; }
     }
     return 0;
+}
+
+// How many (wave, stage) pairs of a two-ring table hold a cell with a boundary facet: stage 1 runs every role, stage 2 the roles below
+// n_mid, stage 3 those below n_inner, and a wave is 64 consecutive PHYSICAL lanes.  Each such pair is one execution of the boundary
+// pass of swe_tri_finish that a wave without a wall cell branches round.  tile < 0: summed over the table.
+inline long long wall_wave_stages(const TileTable &t, const int *nbr, size_t stride, int nfacets, int wg, int tile = -1)
+{
+    long long pairs = 0;
+    const int n_tiles = (int)t.n_inner.size();
+    for (int tl = tile < 0 ? 0 : tile; tl < (tile < 0 ? n_tiles : tile + 1); tl++) {
+        unsigned waves[3] = {0u, 0u, 0u};
+        for (int l = 0; l < wg; l++) {
+            const int c = t.cell[(size_t)tl*wg + l];
+            if (c < 0) continue;
+            bool wall = false;
+            for (int f = 0; f < nfacets; f++) wall = wall || nbr[(size_t)f*stride + c] < 0;
+            if (!wall) continue;
+            const int role = (l - 64*t.rot[tl]) & (wg - 1);
+            waves[0] |= 1u << (l >> 6);
+            if (role < t.n_mid[tl]) waves[1] |= 1u << (l >> 6);
+            if (role < t.n_inner[tl]) waves[2] |= 1u << (l >> 6);
+        }
+        for (int s = 0; s < 3; s++) for (unsigned w = waves[s]; w; w &= w - 1) pairs++;
+    }
+    return pairs;
 }
 
 // ---- the lane records of the three-stage kernel (swe2d_fuse.h: swe_fuse123_kernel) ---------------------------------------------------

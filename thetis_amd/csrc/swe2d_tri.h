@@ -80,11 +80,16 @@ __device__ __forceinline__ void swe_tri_cell(double g, const double u[3], const 
 // bnd: a boundary facet.  It carries finite "neighbour" traces (the callers point it at the cell itself), its flux is evaluated like
 // any other and discarded: the boundary pass of swe_tri_finish / swe_boundary_epilogue adds the facet's true flux to the finished
 // outputs.  (Branch-free on purpose, see swe_stage_kernel; SKIPB: the variants that branch round the evaluation all the same.)
-template <bool NONLIN, bool LF, bool WD, bool SKIPB = false>
+// WAVEB: the six zero assignments sit behind a wave-uniform test, wave_bnd = __any(a lane of the wave has a boundary facet), which the
+// caller forms once per cell body - a wave without one branches round them on the scalar unit instead of issuing six moves with an
+// empty mask and the test of bnd per facet (the three-stage kernel of swe2d_fuse.h: 5425 of the bench mesh's 5733 tiles have no wall
+// cell).  Every lane's fluxes are what they were: zeros with bnd, untouched without.
+template <bool NONLIN, bool LF, bool WD, bool SKIPB = false, bool WAVEB = false>
 __device__ __forceinline__ void swe_tri_facet(double g, double sigma_lf, bool bnd, double ua, double ub, double va, double vb, double ea,
                                               double eb, double ha, double hb, double Ha, double Hb, double ala, double alb, double una,
                                               double unb, double vna, double vnb, double dna, double dnb, double nxs, double nys, double L,
-                                              double rL, double &bua, double &bub, double &bva, double &bvb, double &bea, double &beb)
+                                              double rL, double &bua, double &bub, double &bva, double &bvb, double &bea, double &beb,
+                                              bool wave_bnd = true)
 {
 #pragma clang fp contract(off)
     double Fau = 0.0, Fbu = 0.0, Fav = 0.0, Fbv = 0.0, Fae = 0.0, Fbe = 0.0;
@@ -93,7 +98,12 @@ __device__ __forceinline__ void swe_tri_facet(double g, double sigma_lf, bool bn
         swe_facet_flux<NONLIN, LF, WD>(g, sigma_lf, ua, ub, va, vb, ea, eb, ha, hb, Ha, Hb, una, unb, vna, vnb, ena, enb, dna, dnb, nxs, nys,
                                        L, rL, Fau, Fbu, Fav, Fbv, Fae, Fbe);
     }
-    if (bnd) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }
+    if constexpr (WAVEB) {
+        if (wave_bnd) {
+            asm volatile("");                                  // keeps the block a block: without it the moves are hoisted and the branch goes
+            if (bnd) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }
+        }
+    } else if (bnd) { Fau = 0.0; Fbu = 0.0; Fav = 0.0; Fbv = 0.0; Fae = 0.0; Fbe = 0.0; }
     bua = fma(-0.5, Fau, bua); bub = fma(-0.5, Fbu, bub);
     bva = fma(-0.5, Fav, bva); bvb = fma(-0.5, Fbv, bvb);
     bea = fma(-0.5, Fae, bea); beb = fma(-0.5, Fbe, beb);
