@@ -49,25 +49,19 @@ std::vector<int> tile_records(const TileTable &t, int nfacets)
     return rec;
 }
 
-// allocations and copies: never inside a stream capture (the callers test).  slot_data: what goes to ts.slot_src - null: the table's
-// neighbour codes; the three-stage kernel: the slots' decoded byte offsets, two words per slot
+// allocations and copies: never inside a stream capture (the callers test).  lane_slot: the three-stage kernel's third plane of lane
+// records, the staging slot each lane gathers (the stage pairs gather by lane and facet and have none)
 int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std::vector<int> &counts, const TileTable &t,
-                 const std::vector<unsigned> *slot_data = nullptr)
+                 const std::vector<unsigned> *lane_slot = nullptr)
 {
     HIP_TRY(h, hipMalloc(&ts.tile, rec.size()*sizeof(int)));
     HIP_TRY(h, hipMalloc(&ts.counts, counts.size()*sizeof(int)));
     HIP_TRY(h, hipMemcpy(ts.tile, rec.data(), rec.size()*sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(ts.counts, counts.data(), counts.size()*sizeof(int), hipMemcpyHostToDevice));
-    // the sources of the staging slots: int2 {first, count} per tile, then the neighbour codes (one spare entry: never an empty allocation)
-    std::vector<int> slots;
-    for (size_t i = 0; i + 1 < t.slot_first.size(); i++) { slots.push_back(t.slot_first[i]); slots.push_back(t.slot_first[i + 1] - t.slot_first[i]); }
-    std::vector<int> src(t.slot_src);
-    if (slot_data) src.assign(slot_data->begin(), slot_data->end());
-    src.push_back(0);
-    HIP_TRY(h, hipMalloc(&ts.slots, slots.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&ts.slot_src, src.size()*sizeof(int)));
-    HIP_TRY(h, hipMemcpy(ts.slots, slots.data(), slots.size()*sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(ts.slot_src, src.data(), src.size()*sizeof(int), hipMemcpyHostToDevice));
+    if (lane_slot) {
+        HIP_TRY(h, hipMalloc(&ts.lane_slot, lane_slot->size()*sizeof(unsigned)));
+        HIP_TRY(h, hipMemcpy(ts.lane_slot, lane_slot->data(), lane_slot->size()*sizeof(unsigned), hipMemcpyHostToDevice));
+    }
     ts.n_tiles = (int)t.n_inner.size();
     ts.ring[0] = t.ring[0]; ts.ring[1] = t.ring[1];
     return SWE2D_OK;
@@ -78,8 +72,7 @@ void free_tiles(TileSet &ts)
 {
     if (ts.tile) (void)hipFree(ts.tile);
     if (ts.counts) (void)hipFree(ts.counts);
-    if (ts.slots) (void)hipFree(ts.slots);
-    if (ts.slot_src) (void)hipFree(ts.slot_src);
+    if (ts.lane_slot) (void)hipFree(ts.lane_slot);
     ts = TileSet();
 }
 
@@ -140,8 +133,9 @@ int fuse123_build(Handle *h)
     for (size_t i = 0; i < t.n_inner.size(); i++) { counts.push_back(t.n_inner[i]); counts.push_back(t.n_mid[i] | (t.rot[i] << 16)); }
     // the lanes' and the slots' records, decoded here once per table (swe2d_tiles.h: build_lane_records): the kernel reads no connectivity
     LaneRecords r;
-    build_lane_records(t, h->h_nbr.data(), h->h_cv.data(), h->stride, SWE_FUSE_WG, 8u*SWE_FUSE3_XG, (unsigned)h->stride*8u, r);
-    return upload_tiles(h, h->fuse3, r.lane, counts, t, &r.slot);
+    build_lane_records(t, h->h_nbr.data(), h->h_cv.data(), h->stride, SWE_FUSE_WG, 8u*SWE_FUSE3_XG, (unsigned)h->stride*8u, r,
+                       SWE_FUSE3_STAGING_PLANES ? kStagingPlanes : kStagingSlot6);
+    return upload_tiles(h, h->fuse3, r.lane, counts, t, &r.lane_slot);
 }
 
 // a whole step: state buffer A (U(0)) -> state buffer B (U(3)), then the two change places
@@ -154,8 +148,7 @@ int launch_fuse123(Handle *h, int cell_end)
     fill_stage_args(h, q.st, 0, 0, 1, 0.0, 1.0, kBeta[0], 0, h->n_owned);
     q.rec = static_cast<const int4 *>(h->fuse3.tile);
     q.counts = reinterpret_cast<const int2 *>(h->fuse3.counts);
-    q.slots = reinterpret_cast<const int2 *>(h->fuse3.slots);
-    q.slot_off = reinterpret_cast<const uint2 *>(h->fuse3.slot_src);
+    q.lane_slot = reinterpret_cast<const uint2 *>(h->fuse3.lane_slot);
     q.n_tiles = h->fuse3.n_tiles;
     q.cell_end = cell_end;
     for (int s = 0; s < 3; s++) { q.a0[s] = s ? kAlpha0[s] : 0.0; q.a1[s] = s ? kAlphaIn[s] : 1.0; q.beta[s] = kBeta[s]; }
@@ -304,5 +297,19 @@ int swe2d_solve_stage_pair_cells(swe2d_handle *hh, int32_t cell_end_0, int32_t c
     if (int rc = stage_on_range(h, 0, 0, cell_end_0)) return rc;
     return stage_on_range(h, 1, 0, cell_end_1);
 }
+
+#ifdef SWE_WAVE_TIMING
+// profiling build only (tools/fuse3_phases.py): the phase stamps of the LAST three-stage launch, n_wg sampled workgroups x 4 waves x
+// SWE_F3P_WORDS words (swe2d_fuse.h); out[0..2] of info = words per wave, stamps per wave, the most workgroups the buffer samples
+int swe2d_debug_read_fuse3_phases(swe2d_handle *hh, unsigned long long *out, int32_t n_wg, int32_t info[3])
+{
+    Handle *h = H(hh);
+    if (!h || !info || n_wg < 0 || n_wg > SWE_F3P_MAX_WG) return SWE2D_ERR_INVALID_ARGUMENT;
+    info[0] = SWE_F3P_WORDS; info[1] = SWE_F3P_STAMPS; info[2] = SWE_F3P_MAX_WG;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (n_wg > 0) HIP_TRY(h, hipMemcpyFromSymbol(out, HIP_SYMBOL(swe_fuse3_phase), sizeof(unsigned long long)*4*SWE_F3P_WORDS*(size_t)n_wg));
+    return SWE2D_OK;
+}
+#endif
 
 }  // extern "C"

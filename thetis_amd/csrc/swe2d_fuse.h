@@ -213,6 +213,13 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 // evaluating them again: no register lives longer for it.  The room is the staging area's, which moves INTO P1: nobody reads or writes
 // P1 before stage 1's results go there, and those now wait for one more barrier (every lane has read its traces of U(0)).
 // 25 planes of 256 doubles = 51.2 KB, three workgroups per CU as before (47.6 KB).
+//
+// The staging area (round 22) has the layout of the state planes (swe2d_tiles.h: kStagingPlanes): the lane that gathers a slot writes
+// the slot's six values at its OWN index of six planes of P1 - component c on the reader's node f + 1 to plane 3c, on its node f to
+// plane 3c + 1 - as it writes its own state to P0: conflict-free, and no slot number is formed.  Every trace of stage 1 is then 3*256
+// doubles from the previous component's, outside the tile as inside: stage 1 takes SWE_TR_BYTES_INSIDE as stages 2 and 3 do, the
+// select of the component step and its additions (24 integer VALU per body) go, and the DS offsets are immediates.  Which slot a lane
+// gathers, if any, it reads from a third plane of its record (lane_slot), next to the other two: nothing waits for a per-tile word first.
 #ifndef SWE_FUSE3_MAX_OUT
 #define SWE_FUSE3_MAX_OUT 224                           // staging slots (a ring-2 cell has at most two facets towards the outside)
 #endif
@@ -221,9 +228,14 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SWE_FUSE_MIN_WG) void swe_fuse12_kerne
 #endif
 #define SWE_FUSE3_NGEO 7                                // Lf[3], 1/Lf[3], 1/twoA
 #define SWE_FUSE3_GEO (18*SWE_FUSE_WG)                  // the records follow P0 and P1
+#ifndef SWE_FUSE3_STAGING_PLANES
+#define SWE_FUSE3_STAGING_PLANES 1                      // 0: the staging area of rounds 6-21, [slot][6] (A/B builds)
+#endif
 #define SWE_FUSE3_XG (SWE_FUSE3_GEOM ? 9*SWE_FUSE_WG : 18*SWE_FUSE_WG)       // the staging area: P1 while stage 1 runs
-#define SWE_FUSE3_LDS (SWE_FUSE3_GEOM ? SWE_FUSE3_GEO + SWE_FUSE3_NGEO*SWE_FUSE_WG : SWE_FUSE3_XG + 6*SWE_FUSE3_MAX_OUT)
-static_assert(6*SWE_FUSE3_MAX_OUT <= 9*SWE_FUSE_WG, "the staging area must fit P1");
+#define SWE_FUSE3_XG_DOUBLES (SWE_FUSE3_STAGING_PLANES ? 8*SWE_FUSE_WG : 6*SWE_FUSE3_MAX_OUT)
+#define SWE_FUSE3_LDS (SWE_FUSE3_GEOM ? SWE_FUSE3_GEO + SWE_FUSE3_NGEO*SWE_FUSE_WG : SWE_FUSE3_XG + SWE_FUSE3_XG_DOUBLES)
+static_assert(SWE_FUSE3_XG_DOUBLES <= 9*SWE_FUSE_WG, "the staging area must fit P1");
+static_assert(SWE_FUSE3_MAX_OUT <= 4*(SWE_FUSE_WG/4 - 1) + 4 && SWE_FUSE3_MAX_OUT <= SWE_FUSE_WG, "a lane per staging slot");
 #ifndef SWE_FUSE3_SRC_MIN_WG
 #define SWE_FUSE3_SRC_MIN_WG 2                          // the source-term instances need 187-199 VGPRs: two workgroups per CU (at three: 80-132 B of scratch per lane)
 #endif
@@ -233,19 +245,44 @@ struct SweFuse3Args {
     const int4 *rec;          // [n_tiles][2][256]: the lane records, decoded on the host (swe2d_tiles.h: build_lane_records) - {cell or -1, the
                               //  three tr words of swe_flow_rhs_facets in bytes}, {8*vertex id x 3, bmarkers}
     const int2 *counts;       // [n_tiles]: {n_inner, n_mid | rot << 16}: roles 0 .. n_inner-1 interior, .. n_mid-1 ring 1; role r on lane (r + 64 rot) & 255
-    const int2 *slots;        // [n_tiles]: {first entry of the tile in slot_off, number of staging slots}
-    const uint2 *slot_off;    // per staging slot the byte offsets into the state planes of its source's two nodes on the shared facet
+    const uint2 *lane_slot;   // [n_tiles][256]: by physical lane, the byte offsets into the state planes of the two nodes on the shared facet
+                              //  of the staging slot this lane gathers, or {~0u, ~0u}: no slot (swe2d_tiles.h: LaneRecords::lane_slot)
     int n_tiles;
     int cell_end;             // stage 3 (the only one that leaves the chip) on cells [0, cell_end): a partition's last stage range
     double a0[3], a1[3], beta[3];   // Shu-Osher weights per stage (swe2d_ssprk33_coefficients)
     double *out;              // 9 planes: U(3), NOT the buffer of U(0)
 };
 
+#ifdef SWE_WAVE_TIMING
+// profiling build only (tools/fuse3_phases.py): the phases of a tile's life.  Every wave of a sample of workgroups spread evenly over the
+// launch stamps the shader clock (s_memtime) at SWE_F3P_STAMPS points, keeps the stamps in scalar registers and writes them behind its
+// last store: swe_fuse3_phase[sample][wave] = {13 stamps, tile, HW_ID | XCC_ID << 32 | flags, 0}.  A stamp waits for its own return
+// (lgkmcnt(0), which also drains the wave's LDS operations) and, where it marks an arrival, takes the arrived registers as operands, so
+// that the compiler's own wait for exactly those loads stands in front of it.  The stamps cost time (about a tenth by the clock's
+// documentation) and forbid overlaps the production kernel has: read shares, not lengths.
+//    0 entry | 1 lane record arrived | 2 the cell's own state and vertices arrived | 3 the slot's six outside traces arrived (a wave
+//    with a slot lane) | 4 behind barrier 1 | 5 end of stage 1's body | 6 behind barrier 2 | 7 behind barrier 3 (P1 written) |
+//    8 end of stage 2's body | 9 behind barrier 4 | 10 behind barrier 5 (P1 written) | 11 end of stage 3's body | 12 stores drained
+#define SWE_F3P_STAMPS 13
+#define SWE_F3P_WORDS 16
+#define SWE_F3P_MAX_WG 8192
+__device__ unsigned long long swe_fuse3_phase[SWE_F3P_MAX_WG][4][SWE_F3P_WORDS];
+#define SWE_F3T(i, ...) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wt[i]) : __VA_ARGS__ : "memory")
+#define SWE_F3T9(i, a, b, c) SWE_F3T(i, "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(c[0]), "v"(c[1]), "v"(c[2]))
+#else
+#define SWE_F3T(i, ...)
+#define SWE_F3T9(i, a, b, c)
+#endif
+
 template <bool NONLIN, bool LF, bool SRC = false>
 __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_MIN_WG) void swe_fuse123_kernel(const SweFuse3Args q)
 {
 #pragma clang fp contract(off)
     __shared__ double lds[SWE_FUSE3_LDS];
+#ifdef SWE_WAVE_TIMING
+    unsigned long long wt[SWE_F3P_STAMPS] = {};
+    SWE_F3T(0, "s"(0));
+#endif
     const SweStageArgs &p = q.st;
     const int tile = swe_logical_block(blockIdx.x, gridDim.x);
     if (tile >= q.n_tiles) return;                         // padding of the grid to a multiple of 8
@@ -270,11 +307,11 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
     // Slot s is the work of physical lane 64*(s & 3) + (s >> 2): the slots are dealt round over the four waves, whatever the tile's
     // rotation - each wave, hence each SIMD, issues the six loads once with a quarter of the slots' lanes active, and the barrier behind
     // the prologue waits for four equal shares instead of one or two full waves (224 slots at most: 56 lanes of a wave).
-    const int2 sl = q.slots[tile];
-    const int slot = ((lane & 63) << 2) | (lane >> 6);
-    const bool has_slot = slot < sl.y;
-    uint2 so = {0u, 0u};                                   // the slot's two byte offsets into the state planes, fetched next to the lane's record
-    if (has_slot) so = q.slot_off[sl.x + slot];
+    // Which slot that is the lane does not ask: its two byte offsets into the state planes lie in the third plane of its record, loaded
+    // with the other two (round 22) - the six loads below are the second trip to memory, as the cell's own are, not the third.
+    const uint2 so = q.lane_slot[(size_t)tile*SWE_FUSE_WG + lane];
+    const bool has_slot = so.x != 0xffffffffu;
+    SWE_F3T(1, "v"(ra.x), "v"(rb.x), "v"(so.x));
 
     int bmarkers = rb.w, bkind1 = 0;
     // per facet the BYTE addresses of component 0's two traces (swe_flow_rhs_facets, SWE_TR_BYTES): 16 bits each
@@ -309,6 +346,10 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         r0[3] = swe_ld(gu, oa, 0); r0[4] = swe_ld(gv, oa, 0); r0[5] = swe_ld(ge, oa, 0);
     }
     if (real) {
+#ifdef SWE_WAVE_TIMING
+        SWE_F3T9(2, px, py, h);                            // (the last loads issued for the cell itself; loads return in order)
+        SWE_F3T9(2, u, v, e);
+#endif
 #pragma unroll
         for (int f = 0; f < 3; f++) {
             const int b = (f + 1) % 3;
@@ -319,12 +360,24 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         for (int i = 0; i < 3; i++) { lds[i*SWE_FUSE_WG + lane] = u[i]; lds[(3 + i)*SWE_FUSE_WG + lane] = v[i]; lds[(6 + i)*SWE_FUSE_WG + lane] = e[i]; }
     }
     if (has_slot) {
+        SWE_F3T(3, "v"(r0[0]), "v"(r0[1]), "v"(r0[2]), "v"(r0[3]), "v"(r0[4]), "v"(r0[5]));
+#if SWE_FUSE3_STAGING_PLANES
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            lds[SWE_LDSI(SWE_FUSE3_XG + 3*c*SWE_FUSE_WG + lane, SWE_FUSE3_LDS)] = r0[c];
+            lds[SWE_LDSI(SWE_FUSE3_XG + (3*c + 1)*SWE_FUSE_WG + lane, SWE_FUSE3_LDS)] = r0[3 + c];
+        }
+#else
+        const int slot = ((lane & 63) << 2) | (lane >> 6);
 #pragma unroll
         for (int j = 0; j < 6; j++) lds[SWE_LDSI(SWE_FUSE3_XG + 6*slot + j, SWE_FUSE3_LDS)] = r0[j];
+#endif
     }
     __syncthreads();
+    SWE_F3T(4, "s"(0));
     // ---- stage 1 on every cell of the tile: U(1) = U(0) + beta1 dt M^-1 R(U(0)), into P1
     constexpr int GEOM1 = SWE_FUSE3_GEOM ? SWE_GEOM_KEEP : SWE_GEOM_COMPUTE, GEOM23 = SWE_FUSE3_GEOM ? SWE_GEOM_STORED : SWE_GEOM_COMPUTE;
+    constexpr int TRB1 = SWE_FUSE3_STAGING_PLANES ? SWE_TR_BYTES_INSIDE : SWE_TR_BYTES;
     double twoA = 0.0;
     double *const G = lds + SWE_FUSE3_GEO + lane;          // the lane's record of cell constants: G[j*256]
     if (real) {
@@ -333,7 +386,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         double H[3];
         swe_tri_depths<NONLIN, false>(h, e, nullptr, H);
         swe_tri_cell<NONLIN>(p.g, u, v, e, H, nx, ny, bu, bv, be);
-        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1, SWE_TR_BYTES, true>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
+        swe_flow_rhs_facets<NONLIN, LF, SRC, 1, false, SWE_FUSE3_XG, SWE_FUSE_WG, SWE_FUSE3_LDS, GEOM1, TRB1, true>(p, k, u, v, e, h, lds, tr, bmarkers, nx, ny, twoA, bu, bv, be,
                                                                                                      nullptr, nullptr, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { wu[i] = 1.0*u[i]; wv[i] = 1.0*v[i]; we[i] = 1.0*e[i]; }
@@ -341,17 +394,21 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
                                                                     bu, bv, be, wu, wv, we, true, ou, ov, oe, G);
 #pragma unroll
         for (int i = 0; i < 3; i++) { u[i] = ou[i]; v[i] = ov[i]; e[i] = oe[i]; }
+        SWE_F3T9(5, u, v, e);
     }
     if (SWE_FUSE3_GEOM) __syncthreads();                   // every lane has read its traces of U(0): the staging area is P1 again
+    SWE_F3T(6, "s"(0));
     if (real) {
 #pragma unroll
         for (int i = 0; i < 3; i++) { P1[i*SWE_FUSE_WG + lane] = u[i]; P1[(3 + i)*SWE_FUSE_WG + lane] = v[i]; P1[(6 + i)*SWE_FUSE_WG + lane] = e[i]; }
     }
     __syncthreads();
+    SWE_F3T(7, "s"(0));
     // ---- stage 2 on interior + ring 1, stage 3 on the interior: every neighbour is a cell of the tile, traces from P1; the lane's own
     //      U(0) for the weights from P0
-#pragma unroll 1
-    for (int s = 1; s < 3; s++) {
+    // One body, called once per stage with s a constant (round 22; a rolled loop before): the s == 1 arm, the compares that chose the
+    // stage's bound and the copies u = ou that the loop carried round its back edge (9-10 v_mov_b64 per body) are gone.  168 VGPRs, no scratch.
+    auto later_stage = [&](const int s) __attribute__((always_inline)) {
         const int role = (lane - rot64) & (SWE_FUSE_WG - 1);
         const bool act = role < (s == 1 ? n_mid : n_inner) && (s == 1 || k < q.cell_end);
 #ifdef SWE_WAVE_TIMING
@@ -382,9 +439,13 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
             }
             swe_tri_finish<NONLIN, LF, false, true, GEOM23, SWE_FUSE_WG>(p, k, q.beta[s], twoA, u, v, e, h, nullptr, nullptr, nx, ny, bmarkers,
                                                                          bkind1, bu, bv, be, wu, wv, we, true, ou, ov, oe, G);
+#ifdef SWE_WAVE_TIMING
+            if (s == 1) SWE_F3T9(8, ou, ov, oe); else SWE_F3T9(11, ou, ov, oe);
+#endif
         }
         if (s == 1) {
             __syncthreads();                               // every lane has read its traces of U(1)
+            SWE_F3T(9, "s"(0));
             if (act) {
 #pragma unroll
                 for (int i = 0; i < 3; i++) { P1[i*SWE_FUSE_WG + lane] = ou[i]; P1[(3 + i)*SWE_FUSE_WG + lane] = ov[i]; P1[(6 + i)*SWE_FUSE_WG + lane] = oe[i]; }
@@ -392,6 +453,7 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
                 for (int i = 0; i < 3; i++) { u[i] = ou[i]; v[i] = ov[i]; e[i] = oe[i]; }
             }
             __syncthreads();
+            SWE_F3T(10, "s"(0));
         } else if (act) {
             const swe_rsrc_t gou = swe_rsrc(q.out), gov = swe_rsrc(q.out + 3*S), goe = swe_rsrc(q.out + 6*S);
 #pragma unroll
@@ -401,7 +463,9 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
                 swe_st(goe, k8, i*S8, oe[i]);
             }
         }
-    }
+    };
+    later_stage(1);
+    later_stage(2);
 #ifdef SWE_WAVE_TIMING
     // where did the wave run, and how much of the tile's work did it do?  HW_ID | XCC_ID << 32 | stage bodies << 40 | 1 << 44, per
     // wave of the launch: swe_wave_ts read as one array of 6*SWE_WT_MAX words, word 4*blockIdx.x + wave
@@ -411,6 +475,20 @@ __global__ __launch_bounds__(SWE_FUSE_WG, SRC ? SWE_FUSE3_SRC_MIN_WG : SWE_FUSE_
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         (&swe_wave_ts[0][0])[4*blockIdx.x + (lane >> 6)] = (unsigned long long)hw | ((unsigned long long)(xcc & 0xf) << 32)
                                                            | ((unsigned long long)wt_bodies << 40) | (1ull << 44);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the stores of stage 3 have left
+    SWE_F3T(12, "s"(0));
+    const unsigned wt_every = (gridDim.x + SWE_F3P_MAX_WG - 1)/SWE_F3P_MAX_WG;
+    if ((lane & 63) == 0 && blockIdx.x % wt_every == 0) {
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        unsigned long long *const w = swe_fuse3_phase[blockIdx.x/wt_every][lane >> 6];
+#pragma unroll
+        for (int i = 0; i < SWE_F3P_STAMPS; i++) w[i] = wt[i];
+        w[13] = (unsigned long long)tile;
+        w[14] = (unsigned long long)hw | ((unsigned long long)(xcc & 0xf) << 32) | ((unsigned long long)wt_bodies << 40) | (1ull << 44);
+        w[15] = 0ull;
     }
 #endif
 }

@@ -102,9 +102,8 @@ struct TileSet {
     void *tile = nullptr;                               // [n_tiles][256] records: int2, quadrilaterals int4 (SweFuseArgs / SweFuseQuadArgs); two-ring
                                                         // tiles: [n_tiles][2][256] int4, the decoded lane records (SweFuse3Args::rec)
     int *counts = nullptr;                              // [n_tiles] n_inner; two-ring tiles: int2 {n_inner, n_mid | rot << 16}
-    int *slots = nullptr;                               // [n_tiles] int2 {first slot in slot_src, number of staging slots}
-    int *slot_src = nullptr;                            // neighbour code of every staging slot, tile after tile (swe2d_tiles.h); two-ring tiles:
-                                                        // uint2 per slot, its decoded byte offsets (SweFuse3Args::slot_off)
+    unsigned *lane_slot = nullptr;                      // two-ring tiles only: [n_tiles][256] uint2, per lane the decoded byte offsets of the
+                                                        // staging slot it gathers, or {~0u, ~0u} (SweFuse3Args::lane_slot)
     int n_tiles = 0;
     long long ring[2] = {0, 0};                         // cells of ring 1 / ring 2 over all tiles
 };

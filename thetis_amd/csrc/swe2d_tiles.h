@@ -238,19 +238,38 @@ inline long long wall_wave_stages(const TileTable &t, const int *nbr, size_t str
 // Per staging slot, slot[2*(slot_first[tile] + s) ..] = {ob, oa}: the byte offsets into the three state planes of one component
 // (plane length s8 bytes) of the slot's source cell at its node g and at its node (g + 1) % 3, source = slot_src = (cell << 2) | g.
 // The arithmetic is the unsigned 32-bit arithmetic the kernel did: the words are the bits it formed.
+//
+// A third plane, by physical lane again (round 22): lane_slot[(tile*wg + l)*2 ..] = the {ob, oa} of the staging slot that lane l of the
+// tile gathers - slot s is the work of lane lane_of_slot(s, wg) = (wg/4)*(s & 3) + (s >> 2), the slots dealt round over the four waves -
+// or {kNoSlot, kNoSlot} for a lane without one (no offset into a state plane is that large: the planes hold 8-byte values).  A lane
+// reads its own word next to its record, with an address that depends on the tile and the lane alone: one trip to memory, where the
+// per-tile {first, count} and then slot[first + s] were two.
+//
+// kStagingPlanes (round 22) lays the staging area out like the state planes: planes of wg 8-byte values behind xg_bytes, component c of
+// a slot's value on the reader's node f + 1 in plane 3c, the value on its node f in plane 3c + 1, and slot s at index lane_of_slot(s) -
+// the lane that gathers it, which therefore writes its six values where it writes its own state, one plane on: 8-byte stride over the
+// lanes of a wave, no bank conflict (at index s the lanes of a wave would be 32 B apart, four to a bank; [slot][6] had them 192 B
+// apart, sixteen to a bank).  The outside tr words then have the form of the inside ones - component step 3*wg*8 bytes, the two nodes
+// one plane apart - and 8 planes are touched: 3c + 1 <= 7, and lane_of_slot < wg.
+constexpr unsigned kNoSlot = 0xffffffffu;
+enum StagingLayout { kStagingSlot6 = 0, kStagingPlanes = 1 };
+inline unsigned lane_of_slot(unsigned s, int wg) { return (unsigned)(wg/4)*(s & 3u) + (s >> 2); }
+
 struct LaneRecords {
     std::vector<int> lane;                 // [n_tiles][2][wg] int4
     std::vector<unsigned> slot;            // [slot_first[n_tiles]] uint2
+    std::vector<unsigned> lane_slot;       // [n_tiles][wg] uint2
 };
 
 // nbr, cv: [3][stride] neighbour codes and vertex ids (triangles).  xg_bytes: where the staging area starts in LDS; s8: the byte length
-// of a state plane.
+// of a state plane.  staging: how the outside tr words address the staging area.
 inline void build_lane_records(const TileTable &t, const int *nbr, const int *cv, size_t stride, int wg, unsigned xg_bytes, unsigned s8,
-                               LaneRecords &r)
+                               LaneRecords &r, StagingLayout staging = kStagingSlot6)
 {
     const size_t n_tiles = t.n_inner.size();
     r.lane.assign(n_tiles*2*(size_t)wg*4, 0);
     r.slot.assign(2*t.slot_src.size(), 0u);
+    r.lane_slot.assign(n_tiles*(size_t)wg*2, kNoSlot);
     const unsigned plane = 8u*(unsigned)wg;
     for (size_t tile = 0; tile < n_tiles; tile++) {
         for (int l = 0; l < wg; l++) {
@@ -264,8 +283,9 @@ inline void build_lane_records(const TileTable &t, const int *nbr, const int *cv
                 const unsigned w = t.facet[(tile*wg + l)*3 + f], at = w & 0x1ffu;
                 const unsigned g = code >= 0 ? (unsigned)(code & 3) : (unsigned)f, ga = g == 2u ? 0u : g + 1u;
                 const bool outside = (w & kTileOutside) != 0u;
-                const unsigned ab = outside ? xg_bytes + 48u*at : plane*g + 8u*at;
-                const unsigned aa = outside ? xg_bytes + 24u + 48u*at : plane*ga + 8u*at;
+                unsigned ab = outside ? xg_bytes + 48u*at : plane*g + 8u*at;
+                unsigned aa = outside ? xg_bytes + 24u + 48u*at : plane*ga + 8u*at;
+                if (outside && staging == kStagingPlanes) { ab = xg_bytes + 8u*lane_of_slot(at, wg); aa = ab + plane; }
                 a[1 + f] = (int)(ab | (aa << 16));
                 if (code < 0) bm |= (unsigned)(-code) << (8*f);
                 b[f] = (int)((unsigned)cv[(size_t)f*stride + c]*8u);
@@ -278,6 +298,11 @@ inline void build_lane_records(const TileTable &t, const int *nbr, const int *cv
         r.slot[2*s] = kn8 + (g == 0u ? 0u : (g == 1u ? s8 : 2u*s8));
         r.slot[2*s + 1] = kn8 + (g == 0u ? s8 : (g == 1u ? 2u*s8 : 0u));
     }
+    for (size_t tile = 0; tile < n_tiles; tile++)
+        for (int s = t.slot_first[tile]; s < t.slot_first[tile + 1]; s++) {
+            unsigned *ls = &r.lane_slot[(tile*wg + lane_of_slot((unsigned)(s - t.slot_first[tile]), wg))*2];
+            ls[0] = r.slot[2*(size_t)s]; ls[1] = r.slot[2*(size_t)s + 1];
+        }
 }
 
 }  // namespace swe2d_impl

@@ -10,6 +10,10 @@ of one instance and counts its instructions by class and by region.  The regions
     stage 2/3 body  barrier 3 .. end              the rolled loop: body, the barriers and LDS stores of s = 1, the stores of s = 2
                                                   (executed twice; the census counts its text once)
 
+Since round 22 stages 2 and 3 are two copies of one body (the loop is peeled); the text then has six regions,
+    ... stage 2 body (barrier 3 .. 4), P1 store 2 (barrier 4 .. 5), stage 3 body (barrier 5 .. end: body and the stores of U(3)),
+told from the rolled text by the FP64 instructions behind the fifth barrier (the rolled loop has only the stores of s = 2 there).
+
 Counts are of the TEXT (wave-instructions per execution of a region if every branch falls through), not of a run.
 
     python tools/fuse3_census.py                       # this tree, instance <true,true,false>
@@ -46,7 +50,26 @@ sys.path.insert(0, ROOT)
 from thetis_amd import _build  # noqa: E402
 
 CLASSES = ['fp64', 'rsq/rcp/sqrt', 'cndmask/mov', 'int+addr VALU', 'VMEM', 'DS', 'waitcnt/barrier', 'SALU+branch']
-REGIONS = ['prologue', 'stage 1 body', 'P1 store', 'stage 2/3 body']
+ROLLED = ['prologue', 'stage 1 body', 'P1 store', 'stage 2/3 body']
+PEELED = ['prologue', 'stage 1 body', 'P1 store', 'stage 2 body', 'P1 store 2', 'stage 3 body']
+REGIONS = list(ROLLED)
+BODIES = [1, 3]                                              # the regions that hold a stage body
+
+
+def detect_regions(body):
+    """sets REGIONS / BODIES for the text of one instance: peeled when a stage body follows the fifth barrier"""
+    barriers, fp64_behind = 0, 0
+    for line in body:
+        s = line.strip()
+        if 'codeLenInByte' in s:
+            break
+        if not s or s.startswith((';', '.', '//')) or s.endswith(':'):
+            continue
+        mn = s.split()[0]
+        barriers += mn == 's_barrier'
+        fp64_behind += barriers >= 5 and '_f64' in mn
+    REGIONS[:] = PEELED if fp64_behind >= 200 else ROLLED
+    BODIES[:] = [1, 3, 5] if fp64_behind >= 200 else [1, 3]
 
 
 def assembly(unit, csrc, defines=()):
@@ -167,7 +190,7 @@ def split_paths(body):
             region += 1
     where = {t: i for i, (_, k, t) in enumerate(items) if k == 'label'}
     out = {}
-    for r in (1, 3):
+    for r in BODIES:
         idx = [i for i, it in enumerate(items) if it[0] == r]
         lo, hi = idx[0], idx[-1]
         fwd = []                                             # (start, end, mnemonic) of every forward conditional branch of the region
@@ -238,6 +261,7 @@ def main():
     want = 'swe_fuse123_kernelILb{}ELb{}ELb{}EE'.format(*args.instance)
     name = [n for n in fns if want in n and not n.endswith('.kd')]
     assert len(name) == 1, name
+    detect_regions(fns[name[0]])
     counts, mnem, res = census(fns[name[0]])
     print('# ' + cmd)
     print('# ' + name[0])
