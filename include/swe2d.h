@@ -715,6 +715,33 @@ int  swe2d_particles_read(swe2d_handle *h, int32_t particles_id, double *xy, int
 /* the rows recorded since the last read -> out [rows][n][2] (room for `capacity` rows), then the row buffer is empty */
 int  swe2d_particles_read_rows(swe2d_handle *h, int32_t particles_id, double *out, int32_t *n_rows);
 int  swe2d_particles_destroy(swe2d_handle *h, int32_t particles_id);
+/* ---- Opt-in per particle set: random-walk dispersion, timed releases, cell counts.  A set that uses none of them is advanced by
+ * swe2d_particles_advance as before.  swe2d_particles_advance_at is the same ONE launch with the time `t` at which the move ends; it
+ * counts the set's moves (the counter starts at 0 with the set).
+ * Timed releases: a WAITING particle sits at its release position and turns ACTIVE in the first move with t - dt_move >= its release
+ *     time, which moves it already.
+ * Random walk (Visser 1997, uniform deviates), after a midpoint move that arrived or ended at a wall, at (x', k'), dt = dt_move, left
+ *     to right without contraction: K0, K1, K2 the diffusivity at the vertices of k', l0, l1, l2 the coordinates of x' as above,
+ *         Kx = (l0*K0 + l1*K1) + l2*K2;   gx = ((K1-K0)*b.y - (K2-K0)*a.y)/det;   gy = (a.x*(K2-K0) - b.x*(K1-K0))/det
+ *         Ko = Kx + (0.5*dt)*(gx*gx + gy*gy), a negative Ko is 0;   amp = sqrt((6.0*dt)*Ko)   (the correctly rounded square root)
+ *         d = (dt*gx + amp*Rx, dt*gy + amp*Ry);   (x'', k'') = move(x', k', d)   unless d is (0, 0), which is no walk
+ *     An open boundary: EXITED at the crossing; a wall: stopped at the shortened point, one more wall hit (a move can count two), no
+ *     reflection; SWE2D_PARTICLE_MAX_HOPS reached: LOST at the position before the whole advance, nothing else written.
+ *     (w0, w1, w2, w3) = Philox4x32-10(counter = (particle index, moves made before, 0, 0), key = (seed & 0xffffffff, seed >> 32)),
+ *     multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85;
+ *         Rx = 2*(((w0 >> 5)*67108864.0 + (w1 >> 6))*2^-53) - 1,   Ry the same of w2, w3: in [-1, 1), every operation exact. */
+#define SWE2D_PARTICLE_WAITING 3
+/* diffusivity [n_vertices] at the vertices (the numbering of swe2d_mesh.vertex_xy), finite and >= 0, n_vertices that of the mesh,
+ * else SWE2D_ERR_INVALID_ARGUMENT; from now on swe2d_particles_advance_at adds the random walk; synchronises */
+int  swe2d_particles_set_diffusivity(swe2d_handle *h, int32_t particles_id, int32_t n_vertices, const double *diffusivity, uint64_t seed);
+/* release_times [n] (n that of the set, no NaN; +-infinity allowed): ACTIVE and WAITING particles become WAITING where
+ * release_times[p] > t_now and ACTIVE elsewhere; from now on swe2d_particles_advance_at runs the release gate; synchronises */
+int  swe2d_particles_set_release_times(swe2d_handle *h, int32_t particles_id, int32_t n, const double *release_times, double t_now);
+/* one move that ends at time t (asynchronous); arguments as swe2d_particles_advance; dt_move >= 0 for a set with a diffusivity */
+int  swe2d_particles_advance_at(swe2d_handle *h, int32_t particles_id, double dt_move, double t, int32_t n_open, const int32_t *open_markers);
+/* counts [n_cells] (the handle's own numbering): the particles in every cell whose status s has bit s of status_mask set - one
+ * small launch of 32-bit integer atomic adds into a zeroed buffer of the set, so the result does not depend on the order; synchronises */
+int  swe2d_particles_cell_counts(swe2d_handle *h, int32_t particles_id, uint32_t status_mask, int32_t *counts);
 
 /* ---- Reacting tracers: a tracer's source as an expression of tracer fields, evaluated in front of every stage of that tracer.
  * The source term of the reference is inner(source, test)*dx with the live Functions (tracer_eq_2d.py:281-298).  Here a tracer

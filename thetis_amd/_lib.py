@@ -34,6 +34,7 @@ ATM_METHODS = {'LargeYeager2009': 0, 'LargePond1981': 1, 'SmithBanke1975': 2}   
 ATM_RHO_AIR = 1.22                    # include/swe2d.h SWE2D_ATM_RHO_AIR
 STATS_FIXED = 8                       # accumulators of a statistics set besides the 2 per constituent (csrc/swe2d_stats.hip)
 PARTICLE_ACTIVE, PARTICLE_EXITED, PARTICLE_LOST = 0, 1, 2   # include/swe2d.h SWE2D_PARTICLE_*: status of a tracked particle
+PARTICLE_WAITING = 3                  # include/swe2d.h SWE2D_PARTICLE_WAITING: a timed release that has not come yet
 PARTICLE_MAX_HOPS = 64                # include/swe2d.h SWE2D_PARTICLE_MAX_HOPS: cells one walk may visit
 MAX_SECTIONS, MAX_SECTION_TRACERS = 16, 4   # include/swe2d.h SWE2D_MAX_SECTIONS, SWE2D_MAX_SECTION_TRACERS
 SECTION_VALUES = 2 + MAX_SECTION_TRACERS    # include/swe2d.h SWE2D_SECTION_VALUES: transport, area, one per tracer
@@ -264,6 +265,10 @@ SYMBOLS = {
     'swe2d_particles_read': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip, _ip, _ip, _ip]),
     'swe2d_particles_read_rows': (ctypes.c_int, [_H, ctypes.c_int32, _dp, _ip]),
     'swe2d_particles_destroy': (ctypes.c_int, [_H, ctypes.c_int32]),
+    'swe2d_particles_set_diffusivity': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_uint64]),
+    'swe2d_particles_set_release_times': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_double]),
+    'swe2d_particles_advance_at': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, _ip]),
+    'swe2d_particles_cell_counts': (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_uint32, _ip]),
     'swe2d_tracer_set_reaction': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int32, _ip, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp]),
     'swe2d_tracer_set_reaction_constants': (ctypes.c_int, [_H, ctypes.c_int, ctypes.c_int32, _dp]),
     'swe2d_reaction_set_field': (ctypes.c_int, [_H, ctypes.c_int32, _dp]),

@@ -349,6 +349,11 @@ struct Handle {
         double *pos = nullptr;                          // [n][2] x, y
         int *ist = nullptr;                             // cell [n] | status [n] | exit marker [n] | wall hits [n]
         double *out = nullptr;                          // [capacity][n][2] recorded positions
+        double *release = nullptr;                      // [n] release times (swe2d_particles_set_release_times), else null
+        double *kv = nullptr;                           // [n_vertices] diffusivity (swe2d_particles_set_diffusivity), else null
+        int *counts = nullptr;                          // [n_cells] of swe2d_particles_cell_counts, allocated at its first call
+        unsigned long long seed = 0;                    // the Philox key of the random walk
+        unsigned moves = 0;                             // swe2d_particles_advance_at calls so far: the second counter word
     };
     std::vector<Particles> particles;
     // section transports (swe2d_sections.hip): n_lanes > 0 = the handle has sections

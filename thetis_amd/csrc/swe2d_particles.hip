@@ -14,6 +14,12 @@
 // written (more on an exit or a wall hit).  No LDS, no atomics, every particle has exactly one writer.  The plane pointers are taken
 // from the handle when the launch is enqueued, so an advance after a launch that swapped the state buffers (swe_fuse123_kernel)
 // sees the step result, as a probe row does.
+//
+// Opt-in per set (include/swe2d.h has the formulas): swe2d_particles_advance_at launches swe_particle_walk_kernel<TIMED, WALK>, the
+// same lane body with a release gate in front (TIMED: a WAITING particle whose time has come turns ACTIVE) and Visser's random walk
+// behind the midpoint move (WALK: the diffusivity of the cell's three vertices, ten Philox rounds on the counter (particle, move),
+// one IEEE square root and a second walk).  swe_particle_kernel is the <false, false> body: a set without either runs the
+// instructions it ran before these existed.  swe2d_particles_cell_counts is one launch of 32-bit integer atomic adds.
 #include "swe2d_handle.h"
 
 #ifndef SWE_RANGE_CHECK
@@ -127,14 +133,74 @@ __device__ __forceinline__ int swe_particle_walk(const SweParticleArgs &a, doubl
     return SWE_WALK_LOST;
 }
 
-__global__ void __launch_bounds__(256) swe_particle_kernel(SweParticleArgs a)
+// what the opt-in instances read on top of SweParticleArgs: the release gate (TIMED) and the random walk (WALK)
+struct SweParticleExtra {
+    const double *release;                      // [n] release times (TIMED)
+    const double *kv;                           // [n_vertices] diffusivity at the vertices (WALK)
+    double t;                                   // the time at which the move ends (TIMED)
+    unsigned key0, key1;                        // the low and the high half of the seed (WALK)
+    unsigned move;                              // moves the set has made before this one (WALK)
+};
+
+// Philox4x32-10 (Salmon et al. 2011): ten rounds on the counter c under the key (k0, k1), which goes up by the Weyl constants between rounds
+__device__ __forceinline__ void swe_philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u*c[0];
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u*c[2];
+        const unsigned n0 = h1 ^ c[1] ^ k0, n2 = h0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = l1; c[2] = n2; c[3] = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// a deviate on [-1, 1) from 27 + 26 bits of two words: every operation is exact in doubles
+__device__ __forceinline__ double swe_particle_deviate(unsigned wa, unsigned wb)
 {
 #pragma clang fp contract(off)
-    const int p = blockIdx.x*blockDim.x + threadIdx.x;
-    if (p >= a.n) return;
+    return 2.0*(((double)(wa >> 5)*67108864.0 + (double)(wb >> 6))*0x1p-53) - 1.0;
+}
+
+// Visser's (1997) random-walk displacement of particle p at (x, y) in cell k: dt*grad K + sqrt(6 dt K(offset))*R
+__device__ __forceinline__ void swe_particle_dispersion(const SweParticleArgs &a, const SweParticleExtra &e, int p, int k, double x, double y,
+                                                        double &dx, double &dy)
+{
+#pragma clang fp contract(off)
+    const SweParticleCell c = swe_particle_cell(a, k);
+    double m[3];
+    swe_particle_bary(c, x, y, m);
+    const unsigned k4 = (unsigned)k*4u, S4 = (unsigned)a.stride*4u;
+    const swe_rsrc_t rc = swe_rsrc(a.cv), rk = swe_rsrc(e.kv);
+    const double K0 = swe_ld(rk, (unsigned)swe_ldi(rc, k4, 0u)*8u, 0u), K1 = swe_ld(rk, (unsigned)swe_ldi(rc, k4, S4)*8u, 0u),
+                 K2 = swe_ld(rk, (unsigned)swe_ldi(rc, k4, 2u*S4)*8u, 0u);
+    const double Kx = (m[1]*K0 + m[2]*K1) + m[0]*K2;
+    const double gx = ((K1 - K0)*c.by - (K2 - K0)*c.ay)/c.det;
+    const double gy = (c.ax*(K2 - K0) - c.bx*(K1 - K0))/c.det;
+    double Ko = Kx + (0.5*a.dt_move)*(gx*gx + gy*gy);
+    if (Ko < 0.0) Ko = 0.0;
+    const double amp = sqrt((6.0*a.dt_move)*Ko);            // the correctly rounded IEEE square root, as numpy's
+    unsigned w[4] = {(unsigned)p, e.move, 0u, 0u};
+    swe_philox4x32_10(w, e.key0, e.key1);
+    dx = a.dt_move*gx + amp*swe_particle_deviate(w[0], w[1]);
+    dy = a.dt_move*gy + amp*swe_particle_deviate(w[2], w[3]);
+}
+
+// One move of particle p.  TIMED: a WAITING particle whose release time has come turns ACTIVE first.  WALK: the random-walk step
+// follows the midpoint move that arrived or ended at a wall.  <false, false> is the move of a set without either.
+template <bool TIMED, bool WALK>
+__device__ __forceinline__ void swe_particle_move(const SweParticleArgs &a, const SweParticleExtra &e, int p)
+{
+#pragma clang fp contract(off)
     const swe_rsrc_t ri = swe_rsrc(a.ist), rp = swe_rsrc(a.pos);
     const unsigned p4 = (unsigned)p*4u, p16 = (unsigned)p*16u, N4 = (unsigned)a.n*4u;
-    if (swe_ldi(ri, p4, N4) != SWE2D_PARTICLE_ACTIVE) return;
+    const int status = swe_ldi(ri, p4, N4);
+    if (TIMED && status == SWE2D_PARTICLE_WAITING) {
+        if (!(e.t - a.dt_move >= swe_ld(swe_rsrc(e.release), (unsigned)p*8u, 0u))) return;
+        swe_sti(ri, p4, N4, SWE2D_PARTICLE_ACTIVE);
+    } else if (status != SWE2D_PARTICLE_ACTIVE) {
+        return;
+    }
     const int k = swe_ldi(ri, p4, 0u);
     const double x = swe_ld(rp, p16, 0u), y = swe_ld(rp, p16, 8u);
     double u, v, xm, ym, xn, yn;
@@ -146,6 +212,17 @@ __global__ void __launch_bounds__(256) swe_particle_kernel(SweParticleArgs a)
         swe_particle_velocity(a, km, xm, ym, u, v);
         how = swe_particle_walk(a, x, y, k, a.dt_move*u, a.dt_move*v, xn, yn, kn, marker);
     }
+    int hits = how == SWE_WALK_WALL ? 1 : 0;
+    if (WALK && (how == SWE_WALK_ARRIVED || how == SWE_WALK_WALL)) {
+        double dx, dy;
+        swe_particle_dispersion(a, e, p, kn, xn, yn, dx, dy);
+        if (dx != 0.0 || dy != 0.0) {                       // (a zero displacement is no walk: the particle stays where it is)
+            const double xa = xn, ya = yn;
+            const int ka = kn;
+            how = swe_particle_walk(a, xa, ya, ka, dx, dy, xn, yn, kn, marker);
+            if (how == SWE_WALK_WALL) hits++;
+        }
+    }
     if (how == SWE_WALK_LOST) {
         swe_sti(ri, p4, N4, SWE2D_PARTICLE_LOST);
         return;
@@ -156,9 +233,35 @@ __global__ void __launch_bounds__(256) swe_particle_kernel(SweParticleArgs a)
     if (how == SWE_WALK_EXIT) {
         swe_sti(ri, p4, N4, SWE2D_PARTICLE_EXITED);
         swe_sti(ri, p4, 2u*N4, marker);
-    } else if (how == SWE_WALK_WALL) {
+    } else if (!WALK && how == SWE_WALK_WALL) {
         swe_sti(ri, p4, 3u*N4, swe_ldi(ri, p4, 3u*N4) + 1);
     }
+    if (WALK && hits > 0) swe_sti(ri, p4, 3u*N4, swe_ldi(ri, p4, 3u*N4) + hits);    // (the midpoint move's wall and the walk's own)
+}
+
+__global__ void __launch_bounds__(256) swe_particle_kernel(SweParticleArgs a)
+{
+    const int p = blockIdx.x*blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    swe_particle_move<false, false>(a, SweParticleExtra{}, p);
+}
+
+// the opt-in instances: timed releases, the random walk, both
+template <bool TIMED, bool WALK>
+__global__ void __launch_bounds__(256) swe_particle_walk_kernel(SweParticleArgs a, SweParticleExtra e)
+{
+    const int p = blockIdx.x*blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    swe_particle_move<TIMED, WALK>(a, e, p);
+}
+
+// counts[cell] += 1 for every particle whose status is in the mask: integer atomics, so the order does not matter
+__global__ void __launch_bounds__(256) swe_particle_count_kernel(const int *ist, int n, unsigned status_mask, int n_cells, int *counts)
+{
+    const int p = blockIdx.x*blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int k = ist[p], status = ist[(size_t)n + p];
+    if ((unsigned)status < 32u && ((status_mask >> status) & 1u) && (unsigned)k < (unsigned)n_cells) atomicAdd(&counts[k], 1);
 }
 
 namespace {
@@ -180,7 +283,41 @@ void particles_release(Handle::Particles &s)
     if (s.pos) (void)hipFree(s.pos);
     if (s.ist) (void)hipFree(s.ist);
     if (s.out) (void)hipFree(s.out);
+    if (s.release) (void)hipFree(s.release);
+    if (s.kv) (void)hipFree(s.kv);
+    if (s.counts) (void)hipFree(s.counts);
     s = Handle::Particles();
+}
+
+// the bit mask of the open markers of an advance, or false (the handle has the message)
+bool particles_open_mask(Handle *h, int n_open, const int32_t *open_markers, double dt_move, const char *who, unsigned *mask)
+{
+    if (n_open < 0 || n_open > SWE2D_MAX_MARKERS || (n_open > 0 && !open_markers) || !std::isfinite(dt_move)) {
+        fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": bad argument");
+        return false;
+    }
+    *mask = 0u;
+    for (int j = 0; j < n_open; j++) {
+        if (open_markers[j] < 1 || open_markers[j] >= SWE2D_MAX_MARKERS) {
+            fail(h, SWE2D_ERR_INVALID_ARGUMENT, std::string(who) + ": open markers must be in 1..SWE2D_MAX_MARKERS-1");
+            return false;
+        }
+        *mask |= 1u << open_markers[j];
+    }
+    return true;
+}
+
+SweParticleArgs particles_args(const Handle *h, const Handle::Particles *s, double dt_move, unsigned mask)
+{
+    SweParticleArgs a{};
+    a.state = h->state[0];
+    a.cv = h->cv; a.nbr = h->nbr; a.vx = h->vx; a.vy = h->vy;
+    a.pos = s->pos; a.ist = s->ist;
+    a.stride = h->stride;
+    a.dt_move = dt_move;
+    a.n = s->n;
+    a.open_mask = mask;
+    return a;
 }
 
 }  // namespace
@@ -250,27 +387,131 @@ int swe2d_particles_advance(swe2d_handle *hh, int32_t id, double dt_move, int32_
     Handle *h = H(hh);
     Handle::Particles *s = nullptr;
     if (int rc = particles_check(h, id, &s)) return rc;
-    if (n_open < 0 || n_open > SWE2D_MAX_MARKERS || (n_open > 0 && !open_markers) || !std::isfinite(dt_move))
-        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance: bad argument");
     unsigned mask = 0u;
-    for (int j = 0; j < n_open; j++) {
-        if (open_markers[j] < 1 || open_markers[j] >= SWE2D_MAX_MARKERS)
-            return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance: open markers must be in 1..SWE2D_MAX_MARKERS-1");
-        mask |= 1u << open_markers[j];
-    }
+    if (!particles_open_mask(h, n_open, open_markers, dt_move, "swe2d_particles_advance", &mask)) return SWE2D_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    SweParticleArgs a{};
-    a.state = h->state[0];
-    a.cv = h->cv; a.nbr = h->nbr; a.vx = h->vx; a.vy = h->vy;
-    a.pos = s->pos; a.ist = s->ist;
-    a.stride = h->stride;
-    a.dt_move = dt_move;
-    a.n = s->n;
-    a.open_mask = mask;
+    const SweParticleArgs a = particles_args(h, s, dt_move, mask);
     SWE_CHK_SYNC(h->stream);
     hipLaunchKernelGGL(swe_particle_kernel, dim3((unsigned)grid_for(s->n)), dim3(256), 0, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return SWE2D_OK;
+}
+
+int swe2d_particles_set_diffusivity(swe2d_handle *hh, int32_t id, int32_t n_vertices, const double *diffusivity, uint64_t seed)
+{
+    Handle *h = H(hh);
+    if (h && h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_particles_set_diffusivity: particles are tracked on triangles only");
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (n_vertices != h->n_vertices || !diffusivity)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_diffusivity: the table has one value per vertex of the mesh");
+    for (int v = 0; v < n_vertices; v++)
+        if (!(diffusivity[v] >= 0.0) || !std::isfinite(diffusivity[v]))
+            return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_diffusivity: the diffusivity must be finite and not negative");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)n_vertices*sizeof(double);
+    if (!s->kv) {
+        const hipError_t e = hipMalloc(&s->kv, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->kv = nullptr;
+            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_set_diffusivity: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(h, hipMemcpyAsync(s->kv, diffusivity, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                           // the host array may be reused by the caller
+    s->seed = seed;
+    return SWE2D_OK;
+}
+
+int swe2d_particles_set_release_times(swe2d_handle *hh, int32_t id, int32_t n, const double *release_times, double t_now)
+{
+    Handle *h = H(hh);
+    if (h && h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_particles_set_release_times: particles are tracked on triangles only");
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (n != s->n || !release_times || std::isnan(t_now))
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_release_times: one release time per particle");
+    for (int p = 0; p < n; p++)
+        if (std::isnan(release_times[p]))
+            return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_release_times: a release time is not a number");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)n*sizeof(double);
+    if (!s->release) {
+        const hipError_t e = hipMalloc(&s->release, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->release = nullptr;
+            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_set_release_times: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+        }
+    }
+    // ACTIVE <-> WAITING by the new times; EXITED and LOST particles stay what they are
+    std::vector<int> status((size_t)n);
+    HIP_TRY(h, hipMemcpyAsync(status.data(), s->ist + (size_t)n, (size_t)n*sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int p = 0; p < n; p++)
+        if (status[p] == SWE2D_PARTICLE_ACTIVE || status[p] == SWE2D_PARTICLE_WAITING)
+            status[p] = release_times[p] > t_now ? SWE2D_PARTICLE_WAITING : SWE2D_PARTICLE_ACTIVE;
+    HIP_TRY(h, hipMemcpyAsync(s->release, release_times, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(s->ist + (size_t)n, status.data(), (size_t)n*sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SWE2D_OK;
+}
+
+int swe2d_particles_advance_at(swe2d_handle *hh, int32_t id, double dt_move, double t, int32_t n_open, const int32_t *open_markers)
+{
+    Handle *h = H(hh);
+    if (h && h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_particles_advance_at: particles are tracked on triangles only");
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    unsigned mask = 0u;
+    if (!particles_open_mask(h, n_open, open_markers, dt_move, "swe2d_particles_advance_at", &mask)) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (std::isnan(t)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance_at: the time is not a number");
+    if (s->kv && dt_move < 0.0)
+        return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_advance_at: a random walk cannot go back in time (dt_move < 0)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const SweParticleArgs a = particles_args(h, s, dt_move, mask);
+    SweParticleExtra e{};
+    e.release = s->release; e.kv = s->kv;
+    e.t = t;
+    e.key0 = (unsigned)(s->seed & 0xffffffffull); e.key1 = (unsigned)(s->seed >> 32);
+    e.move = s->moves;
+    const dim3 grid((unsigned)grid_for(s->n)), block(256);
+    SWE_CHK_SYNC(h->stream);
+    if (s->release && s->kv) hipLaunchKernelGGL((swe_particle_walk_kernel<true, true>), grid, block, 0, h->stream, a, e);
+    else if (s->kv) hipLaunchKernelGGL((swe_particle_walk_kernel<false, true>), grid, block, 0, h->stream, a, e);
+    else if (s->release) hipLaunchKernelGGL((swe_particle_walk_kernel<true, false>), grid, block, 0, h->stream, a, e);
+    else hipLaunchKernelGGL(swe_particle_kernel, grid, block, 0, h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    s->moves++;
+    return SWE2D_OK;
+}
+
+int swe2d_particles_cell_counts(swe2d_handle *hh, int32_t id, uint32_t status_mask, int32_t *counts)
+{
+    Handle *h = H(hh);
+    if (h && h->npc != 3) return fail(h, SWE2D_ERR_UNSUPPORTED, "swe2d_particles_cell_counts: particles are tracked on triangles only");
+    Handle::Particles *s = nullptr;
+    if (int rc = particles_check(h, id, &s)) return rc;
+    if (!counts) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->n_cells*sizeof(int);
+    if (!s->counts) {
+        const hipError_t e = hipMalloc(&s->counts, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->counts = nullptr;
+            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_cell_counts: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(h, hipMemsetAsync(s->counts, 0, bytes, h->stream));
+    hipLaunchKernelGGL(swe_particle_count_kernel, dim3((unsigned)grid_for(s->n)), dim3(256), 0, h->stream, s->ist, s->n, status_mask,
+                       h->n_cells, s->counts);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(counts, s->counts, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = capture_parity_check(h)) return rc;
+    return flow_check(h);
 }
 
 int swe2d_particles_record(swe2d_handle *hh, int32_t id)

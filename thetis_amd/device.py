@@ -857,6 +857,40 @@ class Swe2dDevice(object):
     def particles_destroy(self, pid):
         self._ck(self.lib.swe2d_particles_destroy(self.h, int(pid)))
 
+    def particles_set_diffusivity(self, pid, diffusivity, seed=0):
+        """random-walk dispersion for the set: ``diffusivity`` a constant or one value per vertex (mesh numbering), finite and not
+        negative; ``seed``: the 64-bit key of the set's deviates.  From now on ``particles_advance_at`` adds the walk."""
+        a = np.asarray(diffusivity, dtype=np.float64)
+        nv = self._keep[1].shape[0]
+        if a.ndim == 0:
+            a = np.full(nv, float(a))
+        elif a.shape == (nv,) and self._vperm is not None:
+            a = a[self._vperm]
+        a = np.ascontiguousarray(a.reshape(-1))
+        self._ck(self.lib.swe2d_particles_set_diffusivity(self.h, int(pid), len(a), _ptr(a), ctypes.c_uint64(int(seed) & (2**64 - 1))))
+
+    def particles_set_release_times(self, pid, release_times, t_now=0.0):
+        """one release time per particle: a particle released after ``t_now`` is WAITING until a move starts at or after its time"""
+        a = np.ascontiguousarray(release_times, dtype=np.float64).reshape(-1)
+        self._ck(self.lib.swe2d_particles_set_release_times(self.h, int(pid), len(a), _ptr(a), float(t_now)))
+
+    def particles_advance_at(self, pid, dt_move, t, open_markers=()):
+        """``particles_advance`` for a set with a diffusivity or release times: the move ends at time ``t`` and is counted"""
+        slots = np.ascontiguousarray([self._slot(m) for m in open_markers], dtype=np.int32)
+        self._ck(self.lib.swe2d_particles_advance_at(self.h, int(pid), float(dt_move), float(t), len(slots),
+                                                     _iptr(slots) if len(slots) else None))
+
+    def particles_cell_counts(self, pid, status=(_lib.PARTICLE_ACTIVE,)):
+        """(n_cells,) int32 in the caller's cell numbering: the particles of the listed status in every cell; synchronises"""
+        mask = 0
+        for s in status:
+            if not 0 <= int(s) < 32:
+                raise ValueError('no particle status {:}'.format(s))
+            mask |= 1 << int(s)
+        out = np.empty(self.n_cells, dtype=np.int32)
+        self._ck(self.lib.swe2d_particles_cell_counts(self.h, int(pid), mask, _iptr(out)))
+        return out[self.inv_perm] if self.perm is not None else out
+
     # -- tracers + limiter
     def _nodal_in(self, a):
         a = np.asarray(a, dtype=np.float64).reshape(self.n_cells, self.npc)

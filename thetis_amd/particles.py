@@ -28,6 +28,28 @@ a bound on the loop, not a tolerance.  ``probe`` is the same walk without conseq
 the crossing or the shortened point; a probe that does not arrive makes the particle LOST as well.  EXITED and LOST particles are
 never touched again.
 
+Three things are opt-in per callback (``diffusivity=K, seed=s``, ``release_times=``, ``cell_counts()`` / ``concentration()``); a callback
+without them runs what it ran before.
+
+Random-walk dispersion (Visser 1997, uniform deviates) follows a midpoint move that arrived or ended at a wall, in the same launch.
+With (x', k') where that move ended, dt = dt_move, K0, K1, K2 the diffusivity at the vertices of k' and l0, l1, l2 the coordinates of
+x' as above, left to right:
+
+    Kx = (l0*K0 + l1*K1) + l2*K2
+    gx = ((K1-K0)*b.y - (K2-K0)*a.y)/det;   gy = (a.x*(K2-K0) - b.x*(K1-K0))/det          (constant per cell)
+    Ko = Kx + (0.5*dt)*(gx*gx + gy*gy), a negative Ko is 0                                  (K half a drift step ahead, by the cell's own extension)
+    amp = sqrt((6.0*dt)*Ko)                                                                 (sqrt(2 K dt/r), r = 1/3 the variance of R; np.sqrt)
+    d = (dt*gx + amp*Rx, dt*gy + amp*Ry);   (x'', k'') = move(x', k', d)                     (d = (0, 0) is no walk)
+
+``move`` is the walk above: an open boundary lets the particle exit, a wall stops it at the shortened point and counts one more hit (so
+a move can count two; particles are not reflected), MAX_HOPS cells make it LOST at the position it had before the whole advance.
+(w0, w1, w2, w3) = Philox4x32-10 of the counter (particle index, moves the set made before, 0, 0) under the key (seed & 0xffffffff,
+seed >> 32), and Rx = 2*(((w0 >> 5)*67108864.0 + (w1 >> 6))*2^-53) - 1, Ry the same of w2, w3: in [-1, 1), every operation exact.  A
+particle's deviates depend on (seed, index, move) alone - not on batching, the launch shape or the other particles.
+
+Timed releases: a particle whose release time lies after the time at which the callback was made is WAITING (3) at its release
+position.  It turns ACTIVE in the first move whose start time t - dt_move is >= its release time, and that move moves it already.
+
 :class:`HostParticles` below is this algorithm in numpy - the documented restatement of the kernel, and the fallback of a device
 class without particle sets.
 """
@@ -40,13 +62,50 @@ from .callback import DiagnosticCallback
 from .pointeval import PointLocator
 from .timeintegrator import StepConsumer
 
-__all__ = ['ParticleTrackerCallback', 'HostParticles', 'ACTIVE', 'EXITED', 'LOST', 'MAX_HOPS']
+__all__ = ['ParticleTrackerCallback', 'HostParticles', 'ACTIVE', 'EXITED', 'LOST', 'WAITING', 'MAX_HOPS', 'philox4x32_10', 'deviates']
 
-ACTIVE, EXITED, LOST = _lib.PARTICLE_ACTIVE, _lib.PARTICLE_EXITED, _lib.PARTICLE_LOST
+ACTIVE, EXITED, LOST, WAITING = _lib.PARTICLE_ACTIVE, _lib.PARTICLE_EXITED, _lib.PARTICLE_LOST, _lib.PARTICLE_WAITING
 MAX_HOPS = _lib.PARTICLE_MAX_HOPS
 WALL_FACTOR = 1.0 - 2.0**-10
 _ARRIVED, _EXIT, _WALL, _WALKING = 0, 1, 2, 3       # how a walk ended (_WALKING after MAX_HOPS cells: lost)
 ROW_BUFFER_BYTES = 64 << 20                         # the default row buffer on the device: as many rows as fit, at least one
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011): ``counter`` (..., 4) and ``key`` (..., 2) 32-bit words -> (..., 4) uint32"""
+    u64, mask = np.uint64, np.uint64(0xffffffff)
+    counter, key = np.asarray(counter, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    c0, c1, c2, c3 = (counter[..., i] for i in range(4))
+    k0, k1 = key[..., 0], key[..., 1]
+    for _ in range(10):
+        p0, p1 = u64(0xD2511F53)*c0, u64(0xCD9E8D57)*c2             # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> u64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> u64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + u64(0x9E3779B9)) & mask, (k1 + u64(0xBB67AE85)) & mask
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def deviates(seed, index, move):
+    """(Rx, Ry) in [-1, 1) of the particles ``index`` in move number ``move`` under the 64-bit ``seed`` (the module text)"""
+    index = np.asarray(index, dtype=np.uint64)
+    seed = int(seed) & (2**64 - 1)
+    counter = np.stack([index, np.full_like(index, int(move) & 0xffffffff), np.zeros_like(index), np.zeros_like(index)], axis=-1)
+    w = philox4x32_10(counter, np.array([seed & 0xffffffff, seed >> 32], dtype=np.uint64)).astype(np.uint64)
+
+    def one(a, b):
+        return 2.0*(((a >> np.uint64(5)).astype(np.float64)*67108864.0 + (b >> np.uint64(6)).astype(np.float64))*2.0**-53) - 1.0
+    return one(w[..., 0], w[..., 1]), one(w[..., 2], w[..., 3])
+
+
+def vertex_diffusivity(value, n_vertices):
+    """the (n_vertices,) table of a diffusivity given as a number or one value per vertex; ValueError unless finite and >= 0"""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(n_vertices, float(a))
+    if a.shape != (n_vertices,):
+        raise ValueError('diffusivity: one value per vertex ({:d}), got shape {:}'.format(n_vertices, a.shape))
+    if not (np.isfinite(a).all() and (a >= 0.0).all()):
+        raise ValueError('diffusivity: the values must be finite and not negative')
+    return np.array(a)
 
 
 class HostParticles(object):
@@ -65,6 +124,20 @@ class HostParticles(object):
         self.marker = np.zeros(n, dtype=np.int32)
         self.hits = np.zeros(n, dtype=np.int32)
         self.rows = []
+        self.kv, self.seed = None, 0                            # set_diffusivity: the vertex table and the key of the deviates
+        self.release = None                                     # set_release_times
+        self.n_moves = 0                                        # advance_at calls so far: the second counter word
+
+    def set_diffusivity(self, diffusivity, seed=0):
+        self.kv, self.seed = vertex_diffusivity(diffusivity, len(self.vx)), int(seed)
+
+    def set_release_times(self, release_times, t_now=0.0):
+        r = np.array(release_times, dtype=np.float64)
+        if r.shape != self.status.shape or np.isnan(r).any():
+            raise ValueError('release_times: one time per particle ({:d}), none of them NaN'.format(len(self.status)))
+        self.release = r
+        live = (self.status == ACTIVE) | (self.status == WAITING)
+        self.status[live] = np.where(r[live] > float(t_now), WAITING, ACTIVE)
 
     def _geometry(self, k):
         v0, v1, v2 = self.cv[k, 0], self.cv[k, 1], self.cv[k, 2]
@@ -127,8 +200,36 @@ class HostParticles(object):
             k[c] = code[inner]
         return how, ox, oy, ok, marker
 
+    def _dispersion(self, p, k, x, y, dt):
+        """the random-walk displacement of the particles ``p`` at (x, y) in the cells ``k`` (the module text)"""
+        g = self._geometry(k)
+        _, _, ax, ay, bx, by, det = g
+        m0, m1, m2 = self._facet_coordinates(g, x, y)
+        K0, K1, K2 = self.kv[self.cv[k, 0]], self.kv[self.cv[k, 1]], self.kv[self.cv[k, 2]]
+        Kx = (m1*K0 + m2*K1) + m0*K2
+        gx = ((K1 - K0)*by - (K2 - K0)*ay)/det
+        gy = (ax*(K2 - K0) - bx*(K1 - K0))/det
+        Ko = Kx + (0.5*dt)*(gx*gx + gy*gy)
+        Ko = np.where(Ko < 0.0, 0.0, Ko)
+        amp = np.sqrt((6.0*dt)*Ko)
+        rx, ry = deviates(self.seed, p, self.n_moves)
+        return dt*gx + amp*rx, dt*gy + amp*ry
+
     def advance(self, uv, dt_move, open_markers=()):
         """one move of every ACTIVE particle in the nodal velocities ``uv`` (N, 3, 2)"""
+        self._move(uv, dt_move, open_markers, False)
+
+    def advance_at(self, uv, dt_move, t, open_markers=()):
+        """``advance`` for a set with release times or a diffusivity: the move ends at time ``t`` and is counted"""
+        dt_move = float(dt_move)
+        if self.kv is not None and dt_move < 0.0:
+            raise ValueError('a random walk cannot go back in time (dt_move < 0)')
+        if self.release is not None:
+            self.status[(self.status == WAITING) & (float(t) - dt_move >= self.release)] = ACTIVE
+        self._move(uv, dt_move, open_markers, self.kv is not None)
+        self.n_moves += 1
+
+    def _move(self, uv, dt_move, open_markers, walk):
         uv = np.asarray(uv, dtype=np.float64).reshape(len(self.cv), 3, 2)
         open_markers = np.asarray(list(open_markers), dtype=np.int64)
         act = np.nonzero(self.status == ACTIVE)[0]
@@ -144,7 +245,16 @@ class HostParticles(object):
             km = np.where(lost, k, km)                          # (a lost probe has no midpoint: its second walk is discarded)
             u, v = self._velocity(uv, km, xm, ym)
             how, xn, yn, kn, marker = self._walk(x, y, k, dt_move*u, dt_move*v, open_markers)
-        lost |= how == _WALKING
+            lost |= how == _WALKING
+            hits = (how == _WALL).astype(np.int32)
+            if walk:
+                w = np.nonzero(~lost & ((how == _ARRIVED) | (how == _WALL)))[0]
+                dx, dy = self._dispersion(act[w], kn[w], xn[w], yn[w], dt_move)
+                go = (dx != 0.0) | (dy != 0.0)                  # (a zero displacement is no walk)
+                w, dx, dy = w[go], dx[go], dy[go]
+                how[w], xn[w], yn[w], kn[w], marker[w] = self._walk(xn[w], yn[w], kn[w], dx, dy, open_markers)
+                lost |= how == _WALKING
+                hits[w] += how[w] == _WALL
         self.status[act[lost]] = LOST
         ok = ~lost
         a = act[ok]
@@ -152,7 +262,12 @@ class HostParticles(object):
         ex = ok & (how == _EXIT)
         self.status[act[ex]] = EXITED
         self.marker[act[ex]] = marker[ex]
-        self.hits[act[ok & (how == _WALL)]] += 1
+        self.hits[a] += hits[ok]
+
+    def cell_counts(self, status=(ACTIVE,)):
+        """(n_cells,) int32: the particles of the listed status in every cell"""
+        sel = np.isin(self.status, np.asarray(list(status), dtype=np.int64))
+        return np.bincount(self.cell[sel], minlength=len(self.cv)).astype(np.int32)
 
     def record(self):
         self.rows.append(self.xy.copy())
@@ -176,10 +291,17 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
     step by step.  Several ranks: ``NotImplementedError`` at the first evaluation; a quadrilateral mesh: at construction; a position
     outside the mesh: ``PointNotInDomainError`` at construction.  Unless ``export_to_hdf5=False`` rank 0 rewrites
     ``<output_directory>/diagnostic_<name>.npz`` at every export.  ``row_capacity``: rows the device keeps before the callback
-    reads them back (default: what fits 64 MiB)."""
+    reads them back (default: what fits 64 MiB).
+
+    ``diffusivity=K`` (a non-negative number or ``Constant``, a CG-P1 ``Function`` or one value per vertex) adds the random-walk
+    dispersion of the module text to every move, with the deviates of ``seed`` (a 64-bit integer); a DG or vector ``K``:
+    ``NotImplementedError``.  ``release_times`` (N,), in simulation time: a particle whose time lies after the time at which the
+    callback is made is WAITING at its release point until a move starts at or after its time.  ``cell_counts()`` and
+    ``concentration()`` turn the cloud into a field.  A set with a diffusivity or release times goes through
+    ``particles_advance_at``; a device class with particle sets but without that call runs :class:`HostParticles`."""
 
     def __init__(self, solver_obj, positions, name='particles', every=1, record_every=1, open_boundaries=(), start_time=None,
-                 end_time=None, export_to_hdf5=True, outputdir=None, row_capacity=None):
+                 end_time=None, export_to_hdf5=True, outputdir=None, row_capacity=None, diffusivity=None, seed=0, release_times=None):
         super(ParticleTrackerCallback, self).__init__(solver_obj, append_to_log=False, start_time=start_time, end_time=end_time)
         self.name = name
         self.export_to_hdf5 = export_to_hdf5
@@ -199,6 +321,17 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         self.row_capacity = int(row_capacity) if row_capacity is not None else max(1, min(1024, ROW_BUFFER_BYTES//(16*max(n, 1))))
         if self.row_capacity < 1:
             raise ValueError('row_capacity must be >= 1')
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2**64:
+            raise ValueError('seed must be a 64-bit unsigned integer')
+        self.diffusivity = None if diffusivity is None else self._vertex_table(diffusivity, mesh)
+        self.release_times = None
+        self._t_made = float(getattr(solver_obj, 'simulation_time', 0.0))
+        if release_times is not None:
+            self.release_times = np.array(release_times, dtype=np.float64)
+            if self.release_times.shape != (n,) or np.isnan(self.release_times).any():
+                raise ValueError('release_times: one time per particle, shape ({:d},), none of them NaN'.format(n))
+        self._timed_or_walking = self.diffusivity is not None or self.release_times is not None
         self.n_advances = 0
         self._times = []                                # the times of the recorded rows
         self._rows = []                                 # rows already read back, (r, N, 2) blocks
@@ -206,6 +339,21 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         self._set = None                                # (device, particle set id)
         self._host = None                               # HostParticles of a device class without particle sets
         self._batch_iteration = 0
+
+    @staticmethod
+    def _vertex_table(K, mesh):
+        """the per-vertex table of the diffusivity ``K``"""
+        from .function import Function
+        if isinstance(K, Function):
+            fs = K.function_space()
+            if fs.family != 'CG' or fs.degree != 1 or fs.vector:
+                raise NotImplementedError('ParticleTrackerCallback: the diffusivity {!r} lives in a {:}{:d}{:} space; the random walk '
+                                          'takes a constant or a scalar CG-P1 field'.format(K.name(), fs.family, fs.degree,
+                                                                                            ' vector' if fs.vector else ''))
+            K = K.dat.data_ro
+        elif not isinstance(K, np.ndarray):
+            K = float(K)                                # a number or a Constant
+        return vertex_diffusivity(K, mesh.num_vertices)
 
     # ---- where the particles live
     def _stepper(self):
@@ -218,12 +366,16 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
             raise NotImplementedError('ParticleTrackerCallback on several ranks: the partitioned driver does not carry particle '
                                       'sets (track the particles on one device)')
         dev = getattr(self._stepper(), 'device', None)
-        if dev is None or not hasattr(dev, 'particles_create'):
+        if dev is None or not hasattr(dev, 'particles_create') or (self._timed_or_walking and not hasattr(dev, 'particles_advance_at')):
             return None
         if self._set is not None and self._set[0] is not dev:
             raise RuntimeError('the time stepper changed its device under a ParticleTrackerCallback')
         if self._set is None:
             self._set = (dev, dev.particles_create(self.initial_positions, self.initial_cells, capacity=self.row_capacity))
+            if self.diffusivity is not None:
+                dev.particles_set_diffusivity(self._set[1], self.diffusivity, self.seed)
+            if self.release_times is not None:
+                dev.particles_set_release_times(self._set[1], self.release_times, self._t_made)
         return self._set
 
     def _host_set(self):
@@ -231,6 +383,10 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
             mesh = self.solver_obj.mesh2d
             self._host = HostParticles(mesh.cells, mesh.vertex_xy, mesh.cell_nbr, mesh.cell_nbr_facet, self.initial_positions,
                                        self.initial_cells)
+            if self.diffusivity is not None:
+                self._host.set_diffusivity(self.diffusivity, self.seed)
+            if self.release_times is not None:
+                self._host.set_release_times(self.release_times, self._t_made)
         return self._host
 
     def _due(self, iteration, t):
@@ -248,10 +404,15 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
 
     def _sample(self, t, device=None, uv=None):
         """one move at time ``t`` (on ``device``, or on the host in the nodal velocities ``uv``) and, when due, one row"""
-        if device is not None:
-            device.particles_advance(self._set[1], self._dt_move(), self.open_boundaries)
+        if not self._timed_or_walking:                  # the set is advanced as it always was
+            if device is not None:
+                device.particles_advance(self._set[1], self._dt_move(), self.open_boundaries)
+            else:
+                self._host_set().advance(uv, self._dt_move(), self.open_boundaries)
+        elif device is not None:
+            device.particles_advance_at(self._set[1], self._dt_move(), t, self.open_boundaries)
         else:
-            self._host_set().advance(uv, self._dt_move(), self.open_boundaries)
+            self._host_set().advance_at(uv, self._dt_move(), t, self.open_boundaries)
         self.n_advances += 1
         if self.n_advances % self.record_every:
             return
@@ -304,8 +465,11 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         if self._host is not None:
             return self._host.read()
         n = len(self.initial_positions)
-        return (self.initial_positions.copy(), self.initial_cells.astype(np.int32), np.full(n, ACTIVE, dtype=np.int32),
-                np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32))
+        status = np.full(n, ACTIVE, dtype=np.int32)
+        if self.release_times is not None:
+            status[self.release_times > self._t_made] = WAITING
+        return (self.initial_positions.copy(), self.initial_cells.astype(np.int32), status, np.zeros(n, dtype=np.int32),
+                np.zeros(n, dtype=np.int32))
 
     def positions(self):
         """(N, 2) current positions (an EXITED particle: where it crossed the boundary); synchronises"""
@@ -315,7 +479,7 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         return self._read()[1]
 
     def status(self):
-        """(N,) ACTIVE / EXITED / LOST"""
+        """(N,) ACTIVE / EXITED / LOST / WAITING"""
         return self._read()[2]
 
     def exit_markers(self):
@@ -335,6 +499,23 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         assert len(rows) == len(self._times), 'the set holds {:d} rows, the host counted {:d}'.format(len(rows), len(self._times))
         return np.array(self._times, dtype=np.float64), rows
 
+    def cell_counts(self, status=(ACTIVE,)):
+        """(n_cells,) int32 in the mesh's numbering: the particles of the listed status in every cell; synchronises"""
+        status = tuple(int(s) for s in status)
+        if self._set is not None:
+            return self._set[0].particles_cell_counts(self._set[1], status)
+        if self._host is not None:
+            return self._host.cell_counts(status)
+        _, cells, st, _, _ = self._read()
+        return np.bincount(cells[np.isin(st, status)], minlength=self.solver_obj.mesh2d.num_cells).astype(np.int32)
+
+    def concentration(self, status=(ACTIVE,)):
+        """a DG0 ``Function``: particles per unit area in every cell"""
+        from .function import Function, get_functionspace
+        mesh = self.solver_obj.mesh2d
+        return Function(get_functionspace(mesh, 'DG', 0), name='{:}_concentration'.format(self.name)).assign(
+            self.cell_counts(status)/mesh.cell_areas())
+
     def excursion(self):
         """(N,) distance of every particle from its release point"""
         return np.hypot(*(self.positions() - self.initial_positions).T)
@@ -347,7 +528,7 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
 
     def export(self):
         """rank 0 rewrites diagnostic_<name>.npz: time (n_rows,), trajectories (n_rows, N, 2), positions, cells, status, exit_markers,
-        wall_hits, initial_positions - one read-back of the particle state and of the rows not read yet"""
+        wall_hits, initial_positions, and of a set with them release_times, seed, diffusivity (per vertex) - one read-back of the particle state and of the rows not read yet"""
         if not self.export_to_hdf5 or getattr(self.solver_obj.comm, 'rank', 0) != 0:
             return
         t, rows = self.trajectories()
@@ -355,6 +536,12 @@ class ParticleTrackerCallback(DiagnosticCallback, StepConsumer):
         data = {'time': t, 'trajectories': rows, 'positions': xy, 'cells': cells, 'status': status, 'exit_markers': markers,
                 'wall_hits': hits, 'initial_positions': self.initial_positions, 'n_advances': np.array(self.n_advances),
                 'dt_move': np.array(self._dt_move()), 'open_boundaries': np.array(self.open_boundaries, dtype=np.int64)}
+        if self._timed_or_walking:
+            data['seed'] = np.array(self.seed, dtype=np.uint64)
+            if self.release_times is not None:
+                data['release_times'] = self.release_times
+            if self.diffusivity is not None:
+                data['diffusivity'] = self.diffusivity
         outdir = self.outputdir or self.solver_obj.options.output_directory
         os.makedirs(outdir, exist_ok=True)
         path = os.path.join(outdir, 'diagnostic_{:}.npz'.format(self.name))
