@@ -1031,6 +1031,39 @@ int  swe2d_sections_rows_reserve(swe2d_handle *h, int32_t capacity);
 int  swe2d_sections_rows_append(swe2d_handle *h);
 int  swe2d_sections_rows_read(swe2d_handle *h, double *values, int64_t *n_unsummable, int32_t *n_rows);
 
+/* ---- Smagorinsky eddy viscosity (csrc/swe2d_smag.hip; thetis_amd/smagorinsky.py) ----
+ * The closure of thetis/utility3d.py:879-997 (SmagorinskyViscosity), whose formula is two-dimensional.  Per triangle K with area A:
+ *  (1) the weak gradient g[c][x] in P1(K) of velocity component c in direction x (the reference's weak_form branch):
+ *      M g = -int_K d_x phi_i u_c dx + sum_f int_f u_hat phi_i n_x ds, M the P1 mass matrix, u_hat the mean of the two traces on an
+ *      interior facet and the own trace on every boundary facet, all integrals in closed form;
+ *  (2) at the 6 points q of the degree-4 rule: D_T = g[0][0] - g[1][1], D_S = g[0][1] + g[1][0], h_q the P1 element size,
+ *      nu_q = (c_s h_q)^2 sqrt(D_T^2 + D_S^2); the cell moments b[i] = A sum_q w_q lambda_i(q) nu_q;
+ *  (3) per vertex v the LUMPED projection nu_v = sum b[i] / sum A/3 over the (cell, node) pairs of v IN THE ORDER OF THE TABLE handed
+ *      to swe2d_smag_set (the reference solves the consistent mass matrix);
+ *  (4) nu_v = max(min_val, min(nu_v, max_v)), max_v = max_const where that is >= 0, else (1/120) h_v^2 / dt with the handle's
+ *      dt at the time of the update; the stage kernels then read background + nu_v, the background being what swe2d_set_viscosity
+ *      was or is given (a constant or a per-vertex field; 0 without one - the SIPG term is then on).
+ * While the closure is on, swe2d_advance, swe2d_advance_forward_euler and swe2d_advance_coupled make the update in front of EVERY
+ * step, from the state the step starts from; the viscosity is frozen over the step's stages.  The host-stepped entry points
+ * (swe2d_solve_stage ...) read the viscosity of the last update.  No atomics: the result does not depend on scheduling.
+ * SWE2D_ERR_UNSUPPORTED: quadrilaterals, a partition (n_owned != n_cells), wetting-drying, set / clear / read inside a stream
+ * capture. */
+#define SWE2D_SMAG_GRADIENT 0   /* out[n_cells][2][2][3]: component, direction, node.  Sets the debug flag: the cell pass runs once
+                                   more on the current state and writes the gradient planes too */
+#define SWE2D_SMAG_MOMENTS  1   /* out[n_cells][3] */
+#define SWE2D_SMAG_NU       2   /* out[n_vertices]: the clipped closure viscosity */
+#define SWE2D_SMAG_TOTAL    3   /* out[n_vertices]: background + closure, what the stage kernels read */
+/* switches the closure on (or replaces its parameters) and makes one update (synchronises before it).  h_elem_vertex[n_vertices] finite;
+ * vertex_cell_ptr[n_vertices + 1], vertex_cell_idx[3 n_cells]: per vertex its (cell << 2 | local node) entries, every pair once */
+int  swe2d_smag_set(swe2d_handle *h, double c_s, const double *h_elem_vertex, double min_val, double max_const_or_negative,
+                    const int32_t *vertex_cell_ptr, const int32_t *vertex_cell_idx);
+/* switches it off (synchronises): the caller's viscosity, or none, is what it was */
+int  swe2d_smag_clear(swe2d_handle *h);
+/* one evaluation from the current state (buffer A) on the handle's stream; no synchronisation */
+int  swe2d_smag_update(swe2d_handle *h);
+/* synchronises; `which`: SWE2D_SMAG_* */
+int  swe2d_smag_read(swe2d_handle *h, int which, double *out);
+
 #ifdef __cplusplus
 }
 #endif

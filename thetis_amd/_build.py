@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 UNITS = ['swe2d_api.hip', 'swe2d_api_flow.hip', 'swe2d_api_tracer.hip', 'swe2d_api_p2p.hip', 'swe2d_api_fuse.hip', 'swe2d_plan.hip',
          'swe2d_k_tri.hip', 'swe2d_k_wd.hip', 'swe2d_k_quad.hip', 'swe2d_k_flow.hip', 'swe2d_k_flow_wd.hip', 'swe2d_k_tracer.hip',
          'swe2d_probe.hip', 'swe2d_turbine.hip', 'swe2d_dfarm.hip', 'swe2d_tide.hip', 'swe2d_atm.hip', 'swe2d_stats.hip',
-         'swe2d_particles.hip', 'swe2d_reaction.hip', 'swe2d_sediment.hip', 'swe2d_sections.hip']
+         'swe2d_particles.hip', 'swe2d_reaction.hip', 'swe2d_sediment.hip', 'swe2d_sections.hip', 'swe2d_smag.hip']
 UNITY = os.path.join(CSRC, 'swe2d_unity.hip')
 OBJ_DIR = os.path.join(CSRC, '.obj')
 LIB = os.path.join(_HERE, 'libswe2d_hip.so')

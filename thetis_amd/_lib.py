@@ -38,6 +38,7 @@ PARTICLE_WAITING = 3                  # include/swe2d.h SWE2D_PARTICLE_WAITING: 
 PARTICLE_MAX_HOPS = 64                # include/swe2d.h SWE2D_PARTICLE_MAX_HOPS: cells one walk may visit
 MAX_SECTIONS, MAX_SECTION_TRACERS = 16, 4   # include/swe2d.h SWE2D_MAX_SECTIONS, SWE2D_MAX_SECTION_TRACERS
 SECTION_VALUES = 2 + MAX_SECTION_TRACERS    # include/swe2d.h SWE2D_SECTION_VALUES: transport, area, one per tracer
+SMAG_GRADIENT, SMAG_MOMENTS, SMAG_NU, SMAG_TOTAL = 0, 1, 2, 3   # include/swe2d.h SWE2D_SMAG_*: what swe2d_smag_read hands out
 PROBE_UV, PROBE_ELEV = -1, -2  # include/swe2d.h SWE2D_PROBE_*: fields of a probe set (a tracer id >= 0 is the third kind)
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_FINITE = 0, -1, -2, -3, -4, -5
 
@@ -301,6 +302,10 @@ SYMBOLS = {
     'swe2d_sections_rows_reserve': (ctypes.c_int, [_H, ctypes.c_int32]),
     'swe2d_sections_rows_append': (ctypes.c_int, [_H]),
     'swe2d_sections_rows_read': (ctypes.c_int, [_H, _dp, ctypes.POINTER(ctypes.c_int64), _ip]),
+    'swe2d_smag_set': (ctypes.c_int, [_H, ctypes.c_double, _dp, ctypes.c_double, ctypes.c_double, _ip, _ip]),
+    'swe2d_smag_clear': (ctypes.c_int, [_H]),
+    'swe2d_smag_update': (ctypes.c_int, [_H]),
+    'swe2d_smag_read': (ctypes.c_int, [_H, ctypes.c_int, _dp]),
 }
 
 _lib = None

@@ -549,6 +549,7 @@ void swe2d_destroy(swe2d_handle *hh)
     reaction_free_all(h);
     sediment_free(h);
     sections_free(h);
+    smag_free(h);
     for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
     for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
     for (auto &t : h->tracers) {
@@ -879,6 +880,20 @@ int swe2d_set_viscosity(swe2d_handle *hh, int enable, const double *nu_vertex, d
 {
     Handle *h = H(hh);
     if (!h) return SWE2D_ERR_INVALID_ARGUMENT;
+    if (h->smag.on) {
+        // the Smagorinsky closure owns nu_v (swe2d_smag.hip): the caller's viscosity is its background, the SIPG term stays on
+        if (enable && !nu_vertex && !(nu_const >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "viscosity must be >= 0");
+        if (enable && !(sipg_factor > 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "sipg_factor must be > 0");
+        if (int rc = upload_vertex_coefficient(h, enable ? nu_vertex : nullptr, &h->smag.bg_v)) return rc;
+        h->smag.bg_const = enable ? nu_const : 0.0;
+        h->smag.visc_caller = enable != 0;
+        if (enable) {
+            h->sipg_factor = sipg_factor;
+            h->visc_grad_div = use_grad_div_viscosity_term ? 1 : 0;
+            h->visc_grad_depth = use_grad_depth_viscosity_term ? 1 : 0;
+        }
+        return SWE2D_OK;
+    }
     if (!enable) { h->visc = false; return SWE2D_OK; }
     if (!nu_vertex && !(nu_const >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "viscosity must be >= 0");
     if (!(sipg_factor > 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "sipg_factor must be > 0");
@@ -922,10 +937,14 @@ int swe2d_advance(swe2d_handle *hh, int n_steps)
     if (int rc = capture_parity_check(h)) return rc;
     RoctxRange range(h, "swe2d_advance");
     // the dataflow kernel, the three-stage kernel, the fused stage pair + stage 3 or three stage launches: the same bits (swe2d_plan.hip)
-    if (!((h->bed.on || h->slide.on) && !h->sed.on)) return step_swe(h, kAdvance, n_steps);
-    // a flow-only handle with bedload or slide: their passes and the bed update behind every step, as swe2d_advance_coupled orders them
+    const bool bed_passes = (h->bed.on || h->slide.on) && !h->sed.on;
+    if (!bed_passes && !h->smag.on) return step_swe(h, kAdvance, n_steps);
+    // Smagorinsky viscosity: its update in front of every step, from the state the step starts from.  A flow-only handle with bedload
+    // or slide: their passes and the bed update behind every step, as swe2d_advance_coupled orders them
     for (int it = 0; it < n_steps; it++) {
+        if (h->smag.on) { if (int rc = smag_update_launch(h)) return rc; }
         if (int rc = step_swe(h, kAdvance, 1)) return rc;
+        if (!bed_passes) continue;
         if (h->bed.on) { if (int rc = bedload_update_launch(h)) return rc; }
         if (h->slide.on) { if (int rc = slide_update_launch(h)) return rc; }
         if (exner_steps(h)) { if (int rc = exner_launch(h)) return rc; }
@@ -946,6 +965,7 @@ int swe2d_advance_forward_euler(swe2d_handle *hh, int n_steps)
         // (a tide table, an atmospheric record: the forcing of the NEW time first, timeintegrator.py:161-162)
         if (h->tide.n > 0) { if (int rc = tide_launch(h, tide_stage_time(h, it, -1))) return rc; }
         if (h->atm.n_t > 0) { if (int rc = atm_launch(h, tide_stage_time(h, it, -1))) return rc; }
+        if (h->smag.on) { if (int rc = smag_update_launch(h)) return rc; }     // Smagorinsky viscosity of the state the step starts from
         // U_new = U + dt M^-1 R(U): stage 0 of the Shu-Osher form; the result becomes buffer A by a pointer swap
         if (int rc = launch_stage(h, 0, 0, 1, 0.0, 1.0, 1.0, 0, h->n_owned)) return rc;
         swap_state_buffers(h);                             // buffer B now holds the state before the step, not a stage solution

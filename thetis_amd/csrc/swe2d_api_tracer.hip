@@ -595,6 +595,7 @@ int swe2d_advance_coupled(swe2d_handle *hh, int n_steps, int tracer_only, int us
     for (int it = 0; it < n_steps; it++) {
         // the shallow-water step as swe2d_advance makes it on a mesh beyond the dataflow kernel: fused stage pair + stage 3 where
         // that covers the handle (cfg 4 on 1 M triangles), stage launches otherwise
+        if (!tracer_only && h->smag.on) { if (int rc = smag_update_launch(h)) return rc; }   // Smagorinsky viscosity of the state the step starts from
         if (!tracer_only) { if (int rc = step_swe(h, kWholeStep, 1)) return rc; }
         else if (forced(h)) h->clock_k_first++;                          // (the forcings' clock counts the steps of this call either way)
         // the reference's order (coupled_timeintegrator_2d.py:100-135): every other tracer, then the sediment model on the new flow -

@@ -272,6 +272,20 @@ struct Handle {
         unsigned long long *words = nullptr;            // [0] bits of the largest beta of the last pass, [1] flagged cells since set
     };
     Slide slide;
+    // Smagorinsky eddy viscosity (swe2d_smag.hip): on = nu_v is rewritten in front of every step, the caller's viscosity is the background
+    struct Smag {
+        bool on = false;
+        bool visc_caller = false;                       // the caller's own viscosity switch (swe2d_set_viscosity), restored by swe2d_smag_clear
+        double cs = 0.0, min_val = 0.0, max_const = -1.0;
+        double *bg_v = nullptr;                         // [n_vertices] the caller's per-vertex viscosity, or null: bg_const
+        double bg_const = 0.0;
+        double *he = nullptr;                           // [n_vertices] element size
+        int *off = nullptr, *ent = nullptr;             // vertex -> (cell << 2 | local node), in the caller's order
+        double *planes = nullptr;                       // b_0 b_1 b_2 | A/3, [stride] each (the cell pass)
+        double *nu_clip = nullptr;                      // [n_vertices] the clipped closure viscosity (the vertex pass)
+        double *grad = nullptr, *grad_out = nullptr;    // debug: 12 gradient planes and their staging, allocated by the first read
+    };
+    Smag smag;
     int tracer_use_lf = 0;
     double tracer_lf_factor = 1.0, tracer_vel_factor = 1.0;
     std::vector<int> host_cells;                 // [n][3] vertex ids as given (limiter default topology)
@@ -538,6 +552,9 @@ inline bool exner_steps(const Handle *h)                // the bed moves after e
 void sediment_free(Handle *h);                          // (swe2d_destroy)
 // ---- section transports (swe2d_sections.hip): frees the piece tables and the rows (swe2d_destroy)
 void sections_free(Handle *h);
+// ---- Smagorinsky eddy viscosity (swe2d_smag.hip)
+int smag_update_launch(Handle *h);                      // in front of a step: nu_v from buffer A (cell pass + vertex pass)
+void smag_free(Handle *h);                              // (swe2d_destroy; hands nu_v back to the caller's viscosity)
 
 }  // namespace swe2d_impl
 using namespace swe2d_impl;

@@ -1139,6 +1139,59 @@ class Swe2dDevice(object):
     def slide_clear(self):
         self._ck(self.lib.swe2d_slide_clear(self.h))
 
+    # -- Smagorinsky eddy viscosity: csrc/swe2d_smag.hip (thetis_amd/smagorinsky.py restates it)
+    def smag_set(self, c_s, h_elem_vertex, min_val=1e-10, max_viscosity=None):
+        """switches the closure on and makes one update; ``h_elem_vertex``: (V,) element size in the caller's numbering;
+        ``max_viscosity``: None = alpha h_v^2 / dt with the handle's dt.  The lumped projection sums a vertex's cells in ascending
+        order of the CALLER's cell numbers, whatever the device numbering."""
+        from .smagorinsky import vertex_cell_table
+        if self.npc != 3:
+            raise NotImplementedError('use_smagorinsky_viscosity: quadrilaterals are not implemented')
+        he = np.asarray(h_elem_vertex, dtype=np.float64).reshape(-1)
+        if self._vperm is not None:
+            he = he[self._vperm]
+        he = np.ascontiguousarray(he)
+        nv = self._keep[1].shape[0]
+        if he.shape[0] != nv:
+            raise ValueError('the element size must have one value per vertex')
+        cells = self._keep[0]                                  # device cells, device vertex ids
+        if self.perm is not None:
+            # rows in the caller's cell order; the entries name the device cells
+            ptr, idx = vertex_cell_table(cells[self.inv_perm], nv)
+            idx = ((self.inv_perm[idx >> 2].astype(np.int64) << 2) | (idx & 3)).astype(np.int32)
+        else:
+            ptr, idx = vertex_cell_table(cells, nv)
+        ptr, idx = np.ascontiguousarray(ptr), np.ascontiguousarray(idx)
+        self._ck(self.lib.swe2d_smag_set(self.h, float(c_s), _ptr(he), float(min_val),
+                                         -1.0 if max_viscosity is None else float(max_viscosity), _iptr(ptr), _iptr(idx)))
+
+    def smag_clear(self):
+        self._ck(self.lib.swe2d_smag_clear(self.h))
+
+    def smag_update(self):
+        """one evaluation from the current state (enqueued)"""
+        self._ck(self.lib.swe2d_smag_update(self.h))
+
+    def _vertex_out(self, a):
+        if self._vperm is None:
+            return a
+        out = np.empty_like(a)
+        out[self._vperm] = a
+        return out
+
+    def smag_read(self, which):
+        """``which``: 'gradient' (N, 2, 2, 3) - the cell pass runs once more on the current state -, 'moments' (N, 3), 'nu' (V,) the
+        clipped closure viscosity, 'total' (V,) what the stage kernels read; caller's numbering"""
+        code = {'gradient': _lib.SMAG_GRADIENT, 'moments': _lib.SMAG_MOMENTS, 'nu': _lib.SMAG_NU, 'total': _lib.SMAG_TOTAL}[which]
+        if code in (_lib.SMAG_NU, _lib.SMAG_TOTAL):
+            out = np.empty(self._keep[1].shape[0])
+            self._ck(self.lib.swe2d_smag_read(self.h, code, _ptr(out)))
+            return self._vertex_out(out)
+        out = np.empty((self.n_cells, 12 if code == _lib.SMAG_GRADIENT else 3))
+        self._ck(self.lib.swe2d_smag_read(self.h, code, _ptr(out)))
+        out = self._nodal_out(out)
+        return out.reshape(self.n_cells, 2, 2, 3) if code == _lib.SMAG_GRADIENT else out
+
     def exner_skipped(self):
         n = ctypes.c_int64(0)
         self._ck(self.lib.swe2d_exner_skipped(self.h, ctypes.byref(n)))

@@ -147,19 +147,23 @@ class FrozenOptions(object):
     name = 'Options'
     _spec = OrderedDict()       # attribute -> (default factory or value, validator)
     _paired = {}                # enum attribute -> (slave attribute, {value: class})
+    _borrowed = OrderedDict()   # like _spec: options the reference keeps in ANOTHER of its classes (its 3D model's), under the same names
 
     def __init__(self):
         object.__setattr__(self, '_isfrozen', False)
-        for key, (default, _) in self._all_spec().items():
+        for key, (default, _) in self._all_spec(borrowed=True).items():
             value = default() if callable(default) and not isinstance(default, Constant) else default
             setattr(self, key, value)
         object.__setattr__(self, '_isfrozen', True)
 
     @classmethod
-    def _all_spec(cls):
+    def _all_spec(cls, borrowed=False):
+        """the options of the reference's class of the same name; ``borrowed``: and the ones taken over from another of its classes"""
         spec = OrderedDict()
         for klass in reversed(cls.__mro__):
             spec.update(getattr(klass, '_spec', {}))
+            if borrowed:
+                spec.update(getattr(klass, '_borrowed', {}))
         return spec
 
     @classmethod
@@ -170,7 +174,7 @@ class FrozenOptions(object):
         return paired
 
     def __setattr__(self, key, value):
-        spec = self._all_spec()
+        spec = self._all_spec(borrowed=True)
         if key not in spec:
             if self._isfrozen and not hasattr(self, key):
                 raise TypeError('Adding new attribute "{:}" to {:} class is forbidden'.format(key, self.__class__.__name__))
@@ -189,13 +193,13 @@ class FrozenOptions(object):
             params = options
         else:
             assert isinstance(options, FrozenOptions), 'options must be a dict or an options object'
-            params = {k: getattr(options, k) for k in options._all_spec()}
+            params = {k: getattr(options, k) for k in options._all_spec(borrowed=True)}
         for key in params:
             setattr(self, key, params[key])
 
     def __str__(self):
         out = '{:} parameters\n'.format(self.name)
-        for k in sorted(self._all_spec()):
+        for k in sorted(self._all_spec(borrowed=True)):
             out += '  {:16s} : {:}\n'.format(k, getattr(self, k))
         return out
 
@@ -465,6 +469,14 @@ class ModelOptions2d(CommonModelOptions):
         # paired enums last so that their slaves exist after construction
         ('swe_timestepper_type', ('CrankNicolson', _enum(*_SWE_STEPPERS))),
         ('tracer_timestepper_type', ('CrankNicolson', _enum(*_TRACER_STEPPERS))),
+    ])
+    # Smagorinsky eddy viscosity added to horizontal_viscosity: options of the reference's 3D model (options.py:1082-1088), whose
+    # closure is two-dimensional; smagorinsky_max_viscosity: the clip, None = the reference's max_h_diff = h^2/(120 dt)
+    # (this build's own)
+    _borrowed = OrderedDict([
+        ('use_smagorinsky_viscosity', (False, _bool)),
+        ('smagorinsky_coefficient', (lambda: Constant(0.1), _constant)),
+        ('smagorinsky_max_viscosity', (None, _positive_float_or_none)),
     ])
     _paired = {
         'swe_timestepper_type': ('swe_timestepper_options', _SWE_STEPPERS),

@@ -170,7 +170,12 @@ class ERKGenericShuOsher(TimeIntegrator):
             else:
                 alpha = float(alpha)
             self.device.set_wetting_and_drying(alpha)
+        # options.use_smagorinsky_viscosity (_push_smagorinsky): the device makes the update in front of every step, or - a device
+        # class without ``smag_set`` - ``_smag_host`` does, on the state read back, step by step
+        self._smag_on_device = False
+        self._smag_host = None
         self._push_fields()
+        self._push_smagorinsky()
         self._push_farms()
         self._push_bcs()
         uv, eta = self.solution.subfunctions
@@ -253,6 +258,8 @@ class ERKGenericShuOsher(TimeIntegrator):
             self._set_field(fid, value(key), vector=vec)
         if changed('viscosity_h'):
             nu = f.get('viscosity_h')
+            if nu is None and getattr(self.equation.options, 'use_smagorinsky_viscosity', False):
+                nu = 0.0                         # the Smagorinsky closure alone: no background, the SIPG term on
             if nu is not None:                   # HorizontalViscosityTerm, shallowwater_eq.py:554-616
                 opts = self.equation.options
                 dev.set_viscosity(self._vertex_coefficient(nu), sipg_factor=float(_const_value(opts.sipg_factor)),
@@ -261,6 +268,53 @@ class ERKGenericShuOsher(TimeIntegrator):
             elif only_changed:
                 dev.set_viscosity(None)
         self._field_signatures = new
+
+    def _push_smagorinsky(self):
+        """options.use_smagorinsky_viscosity: hand the closure to the device (it then rewrites its viscosity in front of every step of
+        a batch), or set up the host restatement for a device class without it."""
+        opts = self.equation.options
+        if not getattr(opts, 'use_smagorinsky_viscosity', False):
+            return
+        from .cgproject import elem_size_p1
+        from .smagorinsky import HostSmagorinsky, check_supported
+        mesh = self.equation.mesh
+        check_supported(opts, mesh, 1 if self.comm is None else self.comm.size)
+        c_s = float(_const_value(opts.smagorinsky_coefficient))
+        h_elem = elem_size_p1(mesh)
+        if hasattr(self.device, 'smag_set'):
+            self.device.smag_set(c_s, h_elem, max_viscosity=opts.smagorinsky_max_viscosity)
+            self._smag_on_device = True
+        else:
+            self._smag_host = HostSmagorinsky(mesh, c_s, h_elem=h_elem, max_viscosity=opts.smagorinsky_max_viscosity)
+
+    def _smag_background(self):
+        nu = self.fields.get('viscosity_h')
+        return 0.0 if nu is None else self._vertex_coefficient(nu)
+
+    def _smag_step(self, host_only=False):
+        """in front of a step the HOST drives: the viscosity of the state the step starts from (the device's own advance calls make
+        the update themselves: ``host_only``)"""
+        if self._smag_host is not None:
+            opts = self.equation.options
+            uv, _ = self.device.get_state()
+            total = self._smag_host.update(uv, self.dt, self._smag_background())
+            self.device.set_viscosity(total, sipg_factor=float(_const_value(opts.sipg_factor)),
+                                      use_grad_div_viscosity_term=opts.use_grad_div_viscosity_term,
+                                      use_grad_depth_viscosity_term=opts.use_grad_depth_viscosity_term)
+        elif self._smag_on_device and not host_only:
+            self.device.smag_update()
+
+    def smagorinsky_viscosity(self):
+        """the clipped Smagorinsky viscosity per vertex of the CURRENT state (without the background): one update, one read"""
+        self._sync_to_device()
+        if self._smag_on_device:
+            self.device.smag_update()
+            return self.device.smag_read('nu')
+        if self._smag_host is not None:
+            uv, _ = self.device.get_state()
+            self._smag_host.update(uv, self.dt, self._smag_background())
+            return self._smag_host.nu
+        raise ValueError('options.use_smagorinsky_viscosity is off')
 
     def _push_farms(self):
         """Upload the tidal turbine farms whose density changed since the last upload (a ``Function.assign`` or a new density between
@@ -443,7 +497,7 @@ class ERKGenericShuOsher(TimeIntegrator):
     @property
     def forced_per_stage(self):
         """a forcing the HOST evaluates in front of every stage even without ``update_forcings``: no batched steps"""
-        return bool(self._host_tides) or self._host_atm is not None
+        return bool(self._host_tides) or self._host_atm is not None or self._smag_host is not None
 
     @property
     def wants_clock(self):
@@ -512,6 +566,7 @@ class ERKGenericShuOsher(TimeIntegrator):
         self._stage_forcings(t + self.c[i_stage]*self.dt, update_forcings)
         if i_stage == 0:
             self._sync_to_device()
+            self._smag_step()
         # (host WRITES to `solution` between the stages of a step are not supported: the device keeps U0 and the stage solutions
         #  in separate buffers; reads see the last completed stage, see _pull_solution)
         self.device.solve_stage(i_stage)
@@ -576,6 +631,7 @@ class ForwardEuler(ERKGenericShuOsher):
         # the reference evaluates the forcings at the NEW time (:161-162); a tide on the device: the library's own launch, by the clock
         self._stage_forcings(t + self.dt, update_forcings, eval_tide=False)
         self._sync_to_device()
+        self._smag_step(host_only=True)
         self._tide_clock(t)
         self.device.advance_forward_euler(1)
         self._device_ahead = True

@@ -188,6 +188,11 @@ class FlowSolver2d(object):
             self.fields[label] = topts.function if topts.function is not None else Function(self.function_spaces.Q_2d, name=label)
         if self.options.sediment_model_options.solve_suspended_sediment:
             self.fields.sediment_2d = Function(self.function_spaces.Q_2d, name='sediment_2d')
+        if self.options.use_smagorinsky_viscosity:
+            # the clipped Smagorinsky viscosity of the current state, read from the device when someone looks
+            from .smagorinsky import check_supported
+            check_supported(self.options, self.mesh2d, self.comm.size)
+            self.fields.smag_visc_2d = Function(self.function_spaces.P1_2d, name='smag_visc_2d')
         # mesh element size: CG-P1 L2 projection of sqrt(cell area), utility.py:620-640 (needed for automatic dt only)
         self.fields.h_elem_size_2d = None
         self.set_wetting_and_drying_alpha()
@@ -349,6 +354,13 @@ class FlowSolver2d(object):
             self.timestepper = coupled_timeintegrator_2d.GeneralCoupledTimeIntegrator2D(self, swe, tracers, bed=bed)
         else:
             self.timestepper = self.get_swe_timestepper(steppers[name])
+        if self.options.use_smagorinsky_viscosity:
+            swe = getattr(self.timestepper, 'swe', self.timestepper)
+            f = self.fields.smag_visc_2d
+
+            def pull():
+                f._data[...] = swe.smagorinsky_viscosity().reshape(f._data.shape)
+            f._pull_hook = pull
         print_output('Using time integrator: {:}'.format(self.timestepper.__class__.__name__))
 
     def compute_mesh_stats(self):
@@ -373,6 +385,7 @@ class FlowSolver2d(object):
         # thetis/field_defs.py
         meta['bathymetry_2d'] = {'name': 'Bathymetry', 'shortname': 'Bathymetry', 'unit': 'm', 'filename': 'bathymetry2d'}
         meta['sediment_2d'] = {'name': 'Sediment', 'shortname': 'Sediment', 'unit': '', 'filename': 'Sediment2d'}
+        meta['smag_visc_2d'] = {'name': 'Smagorinsky viscosity', 'shortname': 'Smag. viscosity', 'unit': 'm2 s-1', 'filename': 'SmagViscosity2d'}
         return meta
 
     def create_exporters(self):
