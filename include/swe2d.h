@@ -401,6 +401,10 @@ int  swe2d_advance_coupled(swe2d_handle *h, int n_steps, int tracer_only, int us
 /* profiling aid: n_times streaming copies of the 9 state planes (9*stride doubles read + written, 8 B per lane) to calibrate
  * the FETCH_SIZE / WRITE_SIZE counters on a known byte count; does not change the state */
 int  swe2d_debug_calibration_copy(swe2d_handle *h, int n_times);
+/* debugging aid: out[0] = bytes, out[1] = allocations of ordinary device memory the library holds right now, over all handles of
+ * the process (a handle's landing zone of swe2d_p2p_create is not counted).  After the last swe2d_destroy both are what they were
+ * before the first swe2d_create: a difference is a leak. */
+int  swe2d_debug_live_device_memory(uint64_t out[2]);
 
 /* ---- multi-GPU plumbing (one process per GPU; the exchange itself is done by the host with RCCL) ----
  * Replaces PyOP2's per-par_loop halo exchange [FD-assumed] by ONE exchange per time step: a partition carries three layers

@@ -15,6 +15,47 @@ extern const double kBeta[3] = {1.0, 0.25, 0.6666666666666666};
 extern const double kAlpha0[3] = {1.0, 0.75, 0.33333333333333337};   // weight of stage_sol[0]
 extern const double kAlphaIn[3] = {0.0, 0.25, 0.6666666666666666};   // weight of the stage's input (stage 0: U0 itself)
 
+}  // namespace swe2d_impl
+
+// the funnel of swe2d_devmem.h
+namespace {
+std::atomic<unsigned long long> g_live_bytes{0ull}, g_live_allocs{0ull};
+std::mutex g_live_mutex;
+std::map<void *, size_t> g_live_size;                   // what swe_dev_free subtracts
+}
+
+int swe_dev_alloc(void **p, size_t bytes)
+{
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return (int)e; }
+    if (!*p) return (int)hipSuccess;                    // (an empty allocation: nothing to count, free or check)
+    { std::lock_guard<std::mutex> lock(g_live_mutex); g_live_size[*p] = bytes; }
+    g_live_bytes += bytes; g_live_allocs += 1ull;
+#ifdef SWE_RANGE_CHECK
+    swe_chk_record(*p, bytes);
+#endif
+    return (int)hipSuccess;
+}
+
+void swe_dev_free(void *p)
+{
+    if (!p) return;
+    size_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        const auto it = g_live_size.find(p);
+        if (it != g_live_size.end()) { bytes = it->second; g_live_size.erase(it); }
+    }
+    g_live_bytes -= bytes; g_live_allocs -= 1ull;
+#ifdef SWE_RANGE_CHECK
+    swe_chk_forget(p);
+#endif
+    (void)hipFree(p);
+}
+
+namespace swe2d_impl {
+
 int fail(Handle *h, int code, const std::string &msg)
 {
     if (h) h->err = msg; else g_create_error = msg;
@@ -216,8 +257,7 @@ int scatter_facet_values(Handle *h, double *planes, int n, const int32_t *cells,
             if (cells[t] < 0 || cells[t] >= h->n_cells || facets[t] < 0 || facets[t] >= h->npc)
                 return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "boundary facet list: cell or facet index out of range");
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (fl.dev) { HIP_TRY(h, hipFree(fl.dev)); fl.dev = nullptr; }
-        HIP_TRY(h, hipMalloc(&fl.dev, 2*(size_t)n*sizeof(int)));
+        HIP_TRY(h, fl.dev.alloc(2*(size_t)n));
         HIP_TRY(h, hipMemcpy(fl.dev, cells, (size_t)n*sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(fl.dev + n, facets, (size_t)n*sizeof(int), hipMemcpyHostToDevice));
         fl.cells.assign(cells, cells + n);
@@ -233,17 +273,17 @@ int scatter_facet_values(Handle *h, double *planes, int n, const int32_t *cells,
     return SWE2D_OK;
 }
 
-int upload_vertex_coefficient(Handle *h, const double *vertex_values, double **dev)
+int upload_vertex_coefficient(Handle *h, const double *vertex_values, DevArray<double> &dev)
 {
     HIP_TRY(h, hipSetDevice(h->device));
     if (!vertex_values) {
-        if (*dev) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(*dev)); *dev = nullptr; }
+        if (dev) { HIP_TRY(h, hipStreamSynchronize(h->stream)); dev.reset(); }
         return SWE2D_OK;
     }
     for (int i = 0; i < h->n_vertices; i++)
         if (!(vertex_values[i] >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "diffusion coefficient must be >= 0");
-    if (!*dev) HIP_TRY(h, hipMalloc(dev, (size_t)h->n_vertices*sizeof(double)));
-    HIP_TRY(h, hipMemcpyAsync(*dev, vertex_values, (size_t)h->n_vertices*sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, dev.ensure((size_t)h->n_vertices));
+    HIP_TRY(h, hipMemcpyAsync(dev, vertex_values, (size_t)h->n_vertices*sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SWE2D_OK;
 }
@@ -253,6 +293,13 @@ int upload_vertex_coefficient(Handle *h, const double *vertex_values, double **d
 extern "C" {
 
 int swe2d_abi_version(void) { return SWE2D_ABI_VERSION; }
+
+int swe2d_debug_live_device_memory(uint64_t out[2])
+{
+    if (!out) return SWE2D_ERR_INVALID_ARGUMENT;
+    out[0] = g_live_bytes.load(); out[1] = g_live_allocs.load();
+    return SWE2D_OK;
+}
 
 int swe2d_fused_pair_info(swe2d_handle *hh, int32_t out[4])
 {
@@ -375,19 +422,19 @@ int swe2d_create(const swe2d_mesh *mesh, const swe2d_params *params, swe2d_handl
     HIP_TRY_C(hipEventCreate(&h->ev1));
     const size_t S = h->stride;
     for (int b = 0; b < 3; b++) {
-        HIP_TRY_C(hipMalloc(&h->state[b], 3*(size_t)npc*S*sizeof(double)));
+        HIP_TRY_C(h->state[b].alloc(3*(size_t)npc*S));
         HIP_TRY_C(hipMemsetAsync(h->state[b], 0, 3*(size_t)npc*S*sizeof(double), h->stream));
     }
-    HIP_TRY_C(hipMalloc(&h->nbr, (size_t)npc*S*sizeof(int)));
-    HIP_TRY_C(hipMalloc(&h->cv, (size_t)npc*S*sizeof(int)));
-    HIP_TRY_C(hipMalloc(&h->vx, (size_t)nv*sizeof(double)));
-    HIP_TRY_C(hipMalloc(&h->vy, (size_t)nv*sizeof(double)));
-    HIP_TRY_C(hipMalloc(&h->vh, (size_t)nv*sizeof(double)));
-    HIP_TRY_C(hipMalloc(&h->stage_uv, 2*(size_t)npc*n*sizeof(double)));
-    HIP_TRY_C(hipMalloc(&h->stage_eta, (size_t)npc*n*sizeof(double)));
+    HIP_TRY_C(h->nbr.alloc((size_t)npc*S));
+    HIP_TRY_C(h->cv.alloc((size_t)npc*S));
+    HIP_TRY_C(h->vx.alloc(nv));
+    HIP_TRY_C(h->vy.alloc(nv));
+    HIP_TRY_C(h->vh.alloc(nv));
+    HIP_TRY_C(h->stage_uv.alloc(2*(size_t)npc*n));
+    HIP_TRY_C(h->stage_eta.alloc((size_t)npc*n));
     h->n_partial_blocks = (h->n_owned + SWE_BLOCK - 1)/SWE_BLOCK;
-    HIP_TRY_C(hipMalloc(&h->partial, 4*(size_t)h->n_partial_blocks*sizeof(double)));
-    HIP_TRY_C(hipMalloc(&h->diag_acc, SWE_DIAG_BUCKETS*SWE_DIAG_ACC*sizeof(unsigned long long)));
+    HIP_TRY_C(h->partial.alloc(4*(size_t)h->n_partial_blocks));
+    HIP_TRY_C(h->diag_acc.alloc(SWE_DIAG_BUCKETS*SWE_DIAG_ACC));
 
     // connectivity -> SoA planes, validated on the way
     std::vector<int> nbr((size_t)npc*S, 0), cv((size_t)npc*S, 0);
@@ -476,8 +523,8 @@ int swe2d_create(const swe2d_mesh *mesh, const swe2d_params *params, swe2d_handl
             p4[kk] = int4{nbr[kk], nbr[S + kk], nbr[2*S + kk], cv[kk]};
             p2[kk] = int2{cv[S + kk], cv[2*S + kk]};
         }
-        HIP_TRY_C(hipMalloc(&h->idx4, (size_t)S*sizeof(int4)));
-        HIP_TRY_C(hipMalloc(&h->idx2, (size_t)S*sizeof(int2)));
+        HIP_TRY_C(h->idx4.alloc(S));
+        HIP_TRY_C(h->idx2.alloc(S));
         HIP_TRY_C(hipMemcpy(h->idx4, p4.data(), (size_t)S*sizeof(int4), hipMemcpyHostToDevice));
         HIP_TRY_C(hipMemcpy(h->idx2, p2.data(), (size_t)S*sizeof(int2), hipMemcpyHostToDevice));
         {   // the 16-B form of the same records (swe_conn_pack): what the stage kernels read
@@ -489,7 +536,7 @@ int swe2d_create(const swe2d_mesh *mesh, const swe2d_params *params, swe2d_handl
                     pc[kk] = swe_conn_pack(kk, nb3, v3);
                     if (pc[kk].w < 0) h->n_conn_escapes++;
                 }
-                HIP_TRY_C(hipMalloc(&h->idxc, (size_t)S*sizeof(int4)));
+                HIP_TRY_C(h->idxc.alloc(S));
                 HIP_TRY_C(hipMemcpy(h->idxc, pc.data(), (size_t)S*sizeof(int4), hipMemcpyHostToDevice));
             }
         }
@@ -507,18 +554,18 @@ int swe2d_create(const swe2d_mesh *mesh, const swe2d_params *params, swe2d_handl
             p4[kk] = int4{vo[0], vo[1], vo[2], 0};
             if (on_bnd) bnd.push_back(kk);
         }
-        HIP_TRY_C(hipMalloc(&h->opp4, (size_t)S*sizeof(int4)));
+        HIP_TRY_C(h->opp4.alloc(S));
         HIP_TRY_C(hipMemcpy(h->opp4, p4.data(), (size_t)S*sizeof(int4), hipMemcpyHostToDevice));
         h->n_bnd = (int)bnd.size();
         if (h->n_bnd) {
-            HIP_TRY_C(hipMalloc(&h->bnd_cells, bnd.size()*sizeof(int)));
+            HIP_TRY_C(h->bnd_cells.alloc(bnd.size()));
             HIP_TRY_C(hipMemcpy(h->bnd_cells, bnd.data(), bnd.size()*sizeof(int), hipMemcpyHostToDevice));
         }
         // dataflow stage loop (swe2d_flow.h): one stage counter per 64-cell block, the status word, and the exchange slots of
         // the rim facets - interior facets whose two cells sit in different blocks - numbered in cell order
         h->flow_blocks = (n + SWE_BLOCK - 1)/SWE_BLOCK;
-        HIP_TRY_C(hipMalloc(&h->flow_flag, (size_t)h->flow_blocks*SWE_FLOW_FLAG_STRIDE*sizeof(unsigned)));
-        HIP_TRY_C(hipMalloc(&h->flow_status, 4*sizeof(unsigned)));
+        HIP_TRY_C(h->flow_flag.alloc((size_t)h->flow_blocks*SWE_FLOW_FLAG_STRIDE));
+        HIP_TRY_C(h->flow_status.alloc(4));
         HIP_TRY_C(hipMemset(h->flow_flag, 0, (size_t)h->flow_blocks*SWE_FLOW_FLAG_STRIDE*sizeof(unsigned)));
         HIP_TRY_C(hipMemset(h->flow_status, 0, 4*sizeof(unsigned)));
         if (int rc = flow_build(h, nullptr)) { g_create_error = h->err; swe2d_destroy(reinterpret_cast<swe2d_handle *>(h)); return rc; }
@@ -540,38 +587,13 @@ void swe2d_destroy(swe2d_handle *hh)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->my_stream) (void)hipStreamSynchronize(h->my_stream);
-    probe_free_all(h);
-    farm_free_all(h);
-    tide_free(h);
-    atm_free(h);
-    stats_free_all(h);
-    particles_free_all(h);
-    reaction_free_all(h);
-    sediment_free(h);
-    sections_free(h);
-    smag_free(h);
-    for (int b = 0; b < 3; b++) if (h->state[b]) (void)hipFree(h->state[b]);
-    for (int i = 0; i < SWE2D_FIELD_COUNT; i++) if (h->field[i]) (void)hipFree(h->field[i]);
-    for (auto &t : h->tracers) {
-        for (int b = 0; b < 3; b++) if (t.buf[b]) (void)hipFree(t.buf[b]);
-        if (t.source) (void)hipFree(t.source);
-        if (t.mu_v) (void)hipFree(t.mu_v);
-        if (t.bc_value_f) (void)hipFree(t.bc_value_f);
-        if (t.bc_vel_f) (void)hipFree(t.bc_vel_f);
-    }
-    void *ptrs[] = {h->nbr, h->cv, h->vx, h->vy, h->vh, h->stage_uv, h->stage_eta, h->partial, h->diag_acc, h->send_cells, h->recv_cells,
-                    h->lim_v2c_off, h->lim_v2c_cell, h->lim_vbf_off, h->lim_vbf_facet, h->lim_tv, h->lim_mean,
-                    h->lim_qmin, h->lim_qmax, h->valpha, h->snapshot[0].data, h->snapshot[1].data, h->bc_field[0], h->bc_field[1], h->bc_field[2], h->bc_field[3], h->nu_v, h->idx4, h->idx2, h->idxc, h->opp4, h->bnd_cells, h->flow_flag, h->flow_status, h->flow_xo4, h->flow_xo2, h->flow_ex, h->flow_xblk, h->flow_xsrc, h->flow_cell, h->flow_xsend, h->flow_xrecv, h->flow_xtick};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (TileSet *ts : {&h->fuse, &h->fuseq, &h->fuse3}) free_tiles(*ts);
-    for (auto &fl : h->facet_lists) if (fl.dev) (void)hipFree(fl.dev);
-    for (void *m : h->p2p.opened) (void)hipIpcCloseMemHandle(m);
-    if (h->p2p.zone) (void)hipFree(h->p2p.zone);
-    if (h->p2p.ctr) (void)hipFree(h->p2p.ctr);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->my_stream) (void)hipStreamDestroy(h->my_stream);
-    delete h;
+    p2p_close(h);                                       // what DevArray does not own: the peers' zones mapped here, my landing zone
+    const hipEvent_t ev0 = h->ev0, ev1 = h->ev1;
+    const hipStream_t my_stream = h->my_stream;
+    delete h;                                           // every DevArray of the handle, while its stream still exists
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (my_stream) (void)hipStreamDestroy(my_stream);
 }
 
 int swe2d_set_stream(swe2d_handle *hh, void *hip_stream)
@@ -628,19 +650,19 @@ int swe2d_state_snapshot_slot(swe2d_handle *hh, int slot, int restore)
     const size_t nb = (size_t)3*h->npc*h->stride*sizeof(double), nt = (size_t)h->npc*h->stride*sizeof(double);
     const size_t total = nb + h->tracers.size()*nt;
     if (restore) {
-        if (!sn.data || sn.bytes != total) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_state_snapshot: nothing to restore");
+        if (sn.data.size() != total) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_state_snapshot: nothing to restore");
         HIP_TRY(h, hipMemcpyAsync(h->state[0], sn.data, nb, hipMemcpyDeviceToDevice, h->stream));
         for (size_t t = 0; t < h->tracers.size(); t++)
-            HIP_TRY(h, hipMemcpyAsync(h->tracers[t].buf[0], (char *)sn.data + nb + t*nt, nt, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->tracers[t].buf[0], sn.data + nb + t*nt, nt, hipMemcpyDeviceToDevice, h->stream));
         h->state_holds_D = sn.holds_D;
         stage_invalidate(h);                               // the stage buffers belong to the steps that are being undone
         return SWE2D_OK;
     }
-    if (sn.data && sn.bytes != total) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(sn.data); sn.data = nullptr; }
-    if (!sn.data) { HIP_TRY(h, hipMalloc(&sn.data, total)); sn.bytes = total; }
+    if (sn.data && sn.data.size() != total) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sn.data.alloc(total));
     HIP_TRY(h, hipMemcpyAsync(sn.data, h->state[0], nb, hipMemcpyDeviceToDevice, h->stream));
     for (size_t t = 0; t < h->tracers.size(); t++)
-        HIP_TRY(h, hipMemcpyAsync((char *)sn.data + nb + t*nt, h->tracers[t].buf[0], nt, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(sn.data + nb + t*nt, h->tracers[t].buf[0], nt, hipMemcpyDeviceToDevice, h->stream));
     sn.holds_D = h->state_holds_D;
     return SWE2D_OK;
 }
@@ -714,7 +736,7 @@ int swe2d_set_bc_field(swe2d_handle *hh, int which, int marker, const double *no
     const int ncomp = (which == 1) ? 2 : 1;
     const size_t bytes = (size_t)2*h->npc*ncomp*h->stride*sizeof(double);
     if (!h->bc_field[which]) {
-        HIP_TRY(h, hipMalloc(&h->bc_field[which], bytes));
+        HIP_TRY(h, h->bc_field[which].alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(h->bc_field[which], 0, bytes, h->stream));
     }
     const size_t n = (size_t)h->n_cells*h->npc;
@@ -738,7 +760,7 @@ int swe2d_set_bc_facets(swe2d_handle *hh, int which, int n_facets, const int32_t
     const int ncomp = (which == 1) ? 2 : 1;
     const size_t bytes = (size_t)2*h->npc*ncomp*h->stride*sizeof(double);
     if (!h->bc_field[which]) {
-        HIP_TRY(h, hipMalloc(&h->bc_field[which], bytes));
+        HIP_TRY(h, h->bc_field[which].alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(h->bc_field[which], 0, bytes, h->stream));
     }
     return scatter_facet_values(h, h->bc_field[which], n_facets, cells, facets, values, ncomp, 2);
@@ -773,8 +795,7 @@ static int set_field_impl(swe2d_handle *hh, int field, const double *nodal, bool
     if (!nodal) {
         if (h->field[field]) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipFree(h->field[field]));
-            h->field[field] = nullptr;
+            h->field[field].reset();
         }
         return SWE2D_OK;
     }
@@ -790,7 +811,7 @@ static int set_field_impl(swe2d_handle *hh, int field, const double *nodal, bool
     if (field == SWE2D_FIELD_LINEAR_DRAG && h->scalar[SWE2D_SCALAR_LINEAR_DRAG] >= 0.0)
         return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "linear drag is already set as a scalar");
     if (!h->field[field]) {
-        HIP_TRY(h, hipMalloc(&h->field[field], (size_t)h->npc*ncomp*h->stride*sizeof(double)));
+        HIP_TRY(h, h->field[field].alloc((size_t)h->npc*ncomp*h->stride));
         HIP_TRY(h, hipMemsetAsync(h->field[field], 0, (size_t)h->npc*ncomp*h->stride*sizeof(double), h->stream));
     }
     // stage through stage_uv (2kN doubles is enough for either shape; n_vertices <= kN)
@@ -861,7 +882,7 @@ int swe2d_set_wetting_and_drying(swe2d_handle *hh, int enable, const double *alp
         h->state_holds_D = false;
     }
     if (!enable) { h->wd = false; return SWE2D_OK; }
-    if (!h->valpha) HIP_TRY(h, hipMalloc(&h->valpha, (size_t)h->n_vertices*sizeof(double)));
+    HIP_TRY(h, h->valpha.ensure((size_t)h->n_vertices));
     HIP_TRY(h, hipMemcpyAsync(h->valpha, alpha_vertex, (size_t)h->n_vertices*sizeof(double), hipMemcpyHostToDevice, h->stream));
     h->wd = true;
     if (h->npc == 4) hipLaunchKernelGGL(swe_wd_clip_kernel<4>, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream,
@@ -884,7 +905,7 @@ int swe2d_set_viscosity(swe2d_handle *hh, int enable, const double *nu_vertex, d
         // the Smagorinsky closure owns nu_v (swe2d_smag.hip): the caller's viscosity is its background, the SIPG term stays on
         if (enable && !nu_vertex && !(nu_const >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "viscosity must be >= 0");
         if (enable && !(sipg_factor > 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "sipg_factor must be > 0");
-        if (int rc = upload_vertex_coefficient(h, enable ? nu_vertex : nullptr, &h->smag.bg_v)) return rc;
+        if (int rc = upload_vertex_coefficient(h, enable ? nu_vertex : nullptr, h->smag.bg_v)) return rc;
         h->smag.bg_const = enable ? nu_const : 0.0;
         h->smag.visc_caller = enable != 0;
         if (enable) {
@@ -897,7 +918,7 @@ int swe2d_set_viscosity(swe2d_handle *hh, int enable, const double *nu_vertex, d
     if (!enable) { h->visc = false; return SWE2D_OK; }
     if (!nu_vertex && !(nu_const >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "viscosity must be >= 0");
     if (!(sipg_factor > 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "sipg_factor must be > 0");
-    int rc = upload_vertex_coefficient(h, nu_vertex, &h->nu_v);
+    int rc = upload_vertex_coefficient(h, nu_vertex, h->nu_v);
     if (rc) return rc;
     h->nu_const = nu_const;
     h->sipg_factor = sipg_factor;

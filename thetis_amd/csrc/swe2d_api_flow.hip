@@ -90,9 +90,7 @@ int flow_build(Handle *h, const int32_t *order)
     }
     // (slot << 6 must fit an int, the exchange array must stay below SWE_FLOW_NOWHERE)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (void *ptr : {(void *)h->flow_xblk, (void *)h->flow_xsrc, (void *)h->flow_xo4, (void *)h->flow_xo2, (void *)h->flow_ex, (void *)h->flow_cell})
-        if (ptr) (void)hipFree(ptr);
-    h->flow_xblk = nullptr; h->flow_xsrc = nullptr; h->flow_xo4 = nullptr; h->flow_xo2 = nullptr; h->flow_ex = nullptr; h->flow_cell = nullptr;
+    h->flow_xblk.reset(); h->flow_xsrc.reset(); h->flow_xo4.reset(); h->flow_xo2.reset(); h->flow_ex.reset(); h->flow_cell.reset();
     // no flow kernel for this handle / this order: a block with more rim facets than the staging area holds (cells numbered without
     // locality), or slot numbers that do not fit
     if (too_many || !((size_t)3*n_slots*SWE_FLOW_SLOT_BYTES < ((size_t)1 << 31) && n_slots < (1 << 25))) return SWE2D_OK;
@@ -101,17 +99,17 @@ int flow_build(Handle *h, const int32_t *order)
     h->flow_x_ready = false;
     h->flow_parity_bytes = (unsigned)((size_t)std::max(n_slots, 1)*SWE_FLOW_SLOT_BYTES);
     h->flow_ex_bytes = (size_t)3*h->flow_parity_bytes;
-    HIP_TRY(h, hipMalloc(&h->flow_xblk, blk.size()*sizeof(int2)));
+    HIP_TRY(h, h->flow_xblk.alloc(blk.size()));
     HIP_TRY(h, hipMemcpy(h->flow_xblk, blk.data(), blk.size()*sizeof(int2), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc(&h->flow_xsrc, xsrc.size()*sizeof(int)));
+    HIP_TRY(h, h->flow_xsrc.alloc(xsrc.size()));
     HIP_TRY(h, hipMemcpy(h->flow_xsrc, xsrc.data(), xsrc.size()*sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc(&h->flow_cell, fcell.size()*sizeof(int)));
+    HIP_TRY(h, h->flow_cell.alloc(fcell.size()));
     HIP_TRY(h, hipMemcpy(h->flow_cell, fcell.data(), fcell.size()*sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc(&h->flow_xo4, p4.size()*sizeof(int4)));
-    HIP_TRY(h, hipMalloc(&h->flow_xo2, p2.size()*sizeof(int2)));
+    HIP_TRY(h, h->flow_xo4.alloc(p4.size()));
+    HIP_TRY(h, h->flow_xo2.alloc(p2.size()));
     HIP_TRY(h, hipMemcpy(h->flow_xo4, p4.data(), p4.size()*sizeof(int4), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->flow_xo2, p2.data(), p2.size()*sizeof(int2), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMalloc(&h->flow_ex, h->flow_ex_bytes));
+    HIP_TRY(h, h->flow_ex.alloc(h->flow_ex_bytes));
     HIP_TRY(h, hipMemset(h->flow_ex, 0, h->flow_ex_bytes));
     // the stage counters restart with the slots
     HIP_TRY(h, hipMemset(h->flow_flag, 0, (size_t)h->flow_blocks*SWE_FLOW_FLAG_STRIDE*sizeof(unsigned)));
@@ -154,10 +152,10 @@ int flow_build_exchange(Handle *h)
         h->flow_push_blocks += anys; h->flow_recv_blocks += anyr;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!h->flow_xsend) HIP_TRY(h, hipMalloc(&h->flow_xsend, (size_t)np*sizeof(int2)));
-    if (!h->flow_xrecv) HIP_TRY(h, hipMalloc(&h->flow_xrecv, (size_t)np*sizeof(int)));
+    HIP_TRY(h, h->flow_xsend.ensure(np));
+    HIP_TRY(h, h->flow_xrecv.ensure(np));
     if (!h->flow_xtick) {
-        HIP_TRY(h, hipMalloc(&h->flow_xtick, (2*SWE_FLOW_MAX_CYCLES + 32)*sizeof(unsigned)));
+        HIP_TRY(h, h->flow_xtick.alloc(2*SWE_FLOW_MAX_CYCLES + 32));
         HIP_TRY(h, hipMemset(h->flow_xtick, 0, (2*SWE_FLOW_MAX_CYCLES + 32)*sizeof(unsigned)));
     }
     HIP_TRY(h, hipMemcpy(h->flow_xsend, xs.data(), (size_t)np*sizeof(int2), hipMemcpyHostToDevice));

@@ -54,12 +54,12 @@ std::vector<int> tile_records(const TileTable &t, int nfacets)
 int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std::vector<int> &counts, const TileTable &t,
                  const std::vector<unsigned> *lane_slot = nullptr)
 {
-    HIP_TRY(h, hipMalloc(&ts.tile, rec.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&ts.counts, counts.size()*sizeof(int)));
+    HIP_TRY(h, ts.tile.alloc(rec.size()));
+    HIP_TRY(h, ts.counts.alloc(counts.size()));
     HIP_TRY(h, hipMemcpy(ts.tile, rec.data(), rec.size()*sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(ts.counts, counts.data(), counts.size()*sizeof(int), hipMemcpyHostToDevice));
     if (lane_slot) {
-        HIP_TRY(h, hipMalloc(&ts.lane_slot, lane_slot->size()*sizeof(unsigned)));
+        HIP_TRY(h, ts.lane_slot.alloc(lane_slot->size()));
         HIP_TRY(h, hipMemcpy(ts.lane_slot, lane_slot->data(), lane_slot->size()*sizeof(unsigned), hipMemcpyHostToDevice));
     }
     ts.n_tiles = (int)t.n_inner.size();
@@ -67,14 +67,6 @@ int upload_tiles(Handle *h, TileSet &ts, const std::vector<int> &rec, const std:
     return SWE2D_OK;
 }
 }  // namespace
-
-void free_tiles(TileSet &ts)
-{
-    if (ts.tile) (void)hipFree(ts.tile);
-    if (ts.counts) (void)hipFree(ts.counts);
-    if (ts.lane_slot) (void)hipFree(ts.lane_slot);
-    ts = TileSet();
-}
 
 // the stage pair's tables (triangles or quadrilaterals).  Not inside a stream capture - such a capture keeps the stage launches, the
 // next call outside one builds
@@ -97,7 +89,7 @@ static int launch_pair(Handle *h, void (*kern)(const Args), int cell_end)
     Args q;
     fill_stage_args(h, q.st, 0, 0, 2, 0.0, 1.0, kBeta[0], 0, h->n_owned);
     q.st.idxc = h->opt[SWE2D_OPT_COMPACT_IDX] == 0 ? nullptr : h->idxc;      // (the 16-B connectivity records: a streaming kernel; triangles only)
-    q.tile = static_cast<decltype(q.tile)>(ts.tile);
+    q.tile = reinterpret_cast<decltype(q.tile)>(ts.tile.get());
     q.n_inner = ts.counts;
     q.n_tiles = ts.n_tiles;
     q.cell_end = cell_end;
@@ -146,9 +138,9 @@ int launch_fuse123(Handle *h, int cell_end)
     if (!h->fuse3.tile) return fail(h, SWE2D_ERR_UNSUPPORTED, "fused stages: no tile tables (not built inside a stream capture)");
     SweFuse3Args q;
     fill_stage_args(h, q.st, 0, 0, 1, 0.0, 1.0, kBeta[0], 0, h->n_owned);
-    q.rec = static_cast<const int4 *>(h->fuse3.tile);
-    q.counts = reinterpret_cast<const int2 *>(h->fuse3.counts);
-    q.lane_slot = reinterpret_cast<const uint2 *>(h->fuse3.lane_slot);
+    q.rec = reinterpret_cast<const int4 *>(h->fuse3.tile.get());
+    q.counts = reinterpret_cast<const int2 *>(h->fuse3.counts.get());
+    q.lane_slot = reinterpret_cast<const uint2 *>(h->fuse3.lane_slot.get());
     q.n_tiles = h->fuse3.n_tiles;
     q.cell_end = cell_end;
     for (int s = 0; s < 3; s++) { q.a0[s] = s ? kAlpha0[s] : 0.0; q.a1[s] = s ? kAlphaIn[s] : 1.0; q.beta[s] = kBeta[s]; }
@@ -215,7 +207,7 @@ int swe2d_fused_set_order(swe2d_handle *hh, const int32_t *cells_in_tile_order)
     std::vector<int> order;
     if (int rc = checked_tile_order(h, cells_in_tile_order, order)) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (TileSet *ts : {&h->fuse, &h->fuseq, &h->fuse3}) free_tiles(*ts);
+    for (TileSet *ts : {&h->fuse, &h->fuseq, &h->fuse3}) *ts = TileSet();
     if (h->fuse_state == -1) h->fuse_state = 0;
     h->fuse_order.swap(order);
     return SWE2D_OK;
@@ -238,7 +230,7 @@ int swe2d_fused_set_triple_tiles(swe2d_handle *hh, const int32_t *cells_in_tile_
         }
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_tiles(h->fuse3);
+    h->fuse3 = TileSet();
     h->fuse3_order.swap(order);
     h->fuse3_start.swap(start);
     return SWE2D_OK;

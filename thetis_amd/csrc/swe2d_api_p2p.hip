@@ -11,6 +11,16 @@ size_t p2p_channel_offset(const int *width, int c, int n_recv)
     return off;
 }
 
+// The zone and the opened mappings are not DevArrays (swe2d_handle.h, Handle::P2p): a mapping is closed, the zone is freed by the
+// call that matches every one of its three kinds.
+void p2p_close(Handle *h)
+{
+    for (void *m : h->p2p.opened) (void)hipIpcCloseMemHandle(m);
+    h->p2p.opened.clear();
+    if (h->p2p.zone) (void)hipFree(h->p2p.zone);
+    h->p2p.zone = nullptr;
+}
+
 }  // namespace swe2d_impl
 
 extern "C" {
@@ -29,19 +39,19 @@ int swe2d_halo_setup(swe2d_handle *hh, int32_t n_send, const int32_t *send_cells
         if (recv_cells[i] < (h->n_owned < h->n_cells ? h->n_owned : 0) || recv_cells[i] >= h->n_cells)
             return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "receive cell is not a ghost cell");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->send_cells) { HIP_TRY(h, hipFree(h->send_cells)); h->send_cells = nullptr; }
-    if (h->recv_cells) { HIP_TRY(h, hipFree(h->recv_cells)); h->recv_cells = nullptr; }
+    h->send_cells.reset();
+    h->recv_cells.reset();
     h->n_send = n_send;
     h->n_recv = n_recv;
     h->h_send.assign(send_cells, send_cells + n_send);
     h->h_recv.assign(recv_cells, recv_cells + n_recv);
     h->flow_x_ready = false;
     if (n_send > 0) {
-        HIP_TRY(h, hipMalloc(&h->send_cells, (size_t)n_send*sizeof(int)));
+        HIP_TRY(h, h->send_cells.alloc(n_send));
         HIP_TRY(h, hipMemcpy(h->send_cells, send_cells, (size_t)n_send*sizeof(int), hipMemcpyHostToDevice));
     }
     if (n_recv > 0) {
-        HIP_TRY(h, hipMalloc(&h->recv_cells, (size_t)n_recv*sizeof(int)));
+        HIP_TRY(h, h->recv_cells.alloc(n_recv));
         HIP_TRY(h, hipMemcpy(h->recv_cells, recv_cells, (size_t)n_recv*sizeof(int), hipMemcpyHostToDevice));
     }
     return SWE2D_OK;
@@ -106,11 +116,11 @@ int swe2d_p2p_create(swe2d_handle *hh, int32_t n_channels, const int32_t *widths
         && hipExtMallocWithFlags(&z.zone, z.zone_bytes, hipDeviceMallocFinegrained) == hipSuccess) z.zone_kind = 2;
     if (!z.zone_kind) {
         (void)hipGetLastError();
-        HIP_TRY(h, hipMalloc(&z.zone, z.zone_bytes));
+        HIP_TRY(h, hipMalloc(&z.zone, z.zone_bytes));     // (the zone is not a DevArray: swe2d_handle.h, Handle::P2p)
         z.zone_kind = 3;
     }
     HIP_TRY(h, hipMemset(z.zone, 0, z.zone_bytes));
-    HIP_TRY(h, hipMalloc(&z.ctr, n_channels*sizeof(SweP2pCounters)));
+    HIP_TRY(h, z.ctr.alloc(n_channels));
     HIP_TRY(h, hipMemset(z.ctr, 0, n_channels*sizeof(SweP2pCounters)));
     HIP_TRY(h, hipDeviceSynchronize());
     return SWE2D_OK;
@@ -154,13 +164,13 @@ int swe2d_p2p_open(swe2d_handle *hh, const void *ipc_handle, void **remote_base)
     HIP_TRY(h, hipMemcpy(probe, &pattern, sizeof(pattern), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(&back, probe, sizeof(back), hipMemcpyDeviceToHost));
     if (back != pattern) return fail(h, SWE2D_ERR_HIP, "swe2d_p2p_open: a copy into the peer's landing zone does not read back");
-    unsigned long long *dback = nullptr;
-    HIP_TRY(h, hipMalloc(&dback, sizeof(*dback)));
-    hipLaunchKernelGGL(swe_p2p_probe_kernel, dim3(1), dim3(64), 0, h->stream, probe, ~pattern, dback);
+    DevArray<unsigned long long> dback;
+    HIP_TRY(h, dback.alloc(1));
+    hipLaunchKernelGGL(swe_p2p_probe_kernel, dim3(1), dim3(64), 0, h->stream, probe, ~pattern, dback.get());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipMemcpy(&back, dback, sizeof(back), hipMemcpyDeviceToHost);
-    (void)hipFree(dback);
+    dback.reset();
     if (e != hipSuccess) return fail(h, SWE2D_ERR_HIP, "swe2d_p2p_open: the probe kernel failed on the peer's landing zone");
     if (back != ~pattern) return fail(h, SWE2D_ERR_HIP, "swe2d_p2p_open: a kernel store into the peer's landing zone does not read back");
     *remote_base = p;

@@ -136,18 +136,14 @@ int limiter_build(Handle *h, int nv, const int *topo /* [n][3] */)
                 bf[bpos[v2]++] = (k << 2) | i;
             }
         }
-    int **ptrs[] = {&h->lim_v2c_off, &h->lim_v2c_cell, &h->lim_vbf_off, &h->lim_vbf_facet, &h->lim_tv};
-    for (int **pp : ptrs) if (*pp) { HIP_TRY(h, hipFree(*pp)); *pp = nullptr; }
-    double **dptrs[] = {&h->lim_mean, &h->lim_qmin, &h->lim_qmax};
-    for (double **pp : dptrs) if (*pp) { HIP_TRY(h, hipFree(*pp)); *pp = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->lim_v2c_off, off.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->lim_v2c_cell, cell.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->lim_vbf_off, boff.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->lim_vbf_facet, bf.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->lim_tv, tv.size()*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->lim_mean, S*sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->lim_qmin, (size_t)nv*sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->lim_qmax, (size_t)nv*sizeof(double)));
+    HIP_TRY(h, h->lim_v2c_off.alloc(off.size()));
+    HIP_TRY(h, h->lim_v2c_cell.alloc(cell.size()));
+    HIP_TRY(h, h->lim_vbf_off.alloc(boff.size()));
+    HIP_TRY(h, h->lim_vbf_facet.alloc(bf.size()));
+    HIP_TRY(h, h->lim_tv.alloc(tv.size()));
+    HIP_TRY(h, h->lim_mean.alloc(S));
+    HIP_TRY(h, h->lim_qmin.alloc(nv));
+    HIP_TRY(h, h->lim_qmax.alloc(nv));
     HIP_TRY(h, hipMemcpy(h->lim_v2c_off, off.data(), off.size()*sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->lim_v2c_cell, cell.data(), cell.size()*sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->lim_vbf_off, boff.data(), boff.size()*sizeof(int), hipMemcpyHostToDevice));
@@ -201,10 +197,10 @@ int swe2d_tracer_add(swe2d_handle *hh, int *tracer_id)
         t.bc_vel_kind[m] = 0; t.bc_u[m] = 0.0; t.bc_v[m] = 0.0; t.bc_vel_field[m] = 0;
     }
     for (int b = 0; b < 3; b++) {
-        HIP_TRY(h, hipMalloc(&t.buf[b], (size_t)h->npc*h->stride*sizeof(double)));
+        HIP_TRY(h, t.buf[b].alloc((size_t)h->npc*h->stride));
         HIP_TRY(h, hipMemsetAsync(t.buf[b], 0, (size_t)h->npc*h->stride*sizeof(double), h->stream));
     }
-    h->tracers.push_back(t);
+    h->tracers.push_back(std::move(t));
     *tracer_id = (int)h->tracers.size() - 1;
     return SWE2D_OK;
 }
@@ -296,7 +292,7 @@ int swe2d_tracer_set_bc_velocity_facets(swe2d_handle *hh, int id, int marker, in
     Handle::Tracer &t = h->tracers[id];
     const size_t bytes = (size_t)4*h->npc*h->stride*sizeof(double);
     if (!t.bc_vel_f) {
-        HIP_TRY(h, hipMalloc(&t.bc_vel_f, bytes));
+        HIP_TRY(h, t.bc_vel_f.alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(t.bc_vel_f, 0, bytes, h->stream));
     }
     t.bc_vel_kind[marker] = kind;
@@ -318,7 +314,7 @@ int swe2d_tracer_set_bc_facets(swe2d_handle *hh, int id, int n_facets, const int
     Handle::Tracer &t = h->tracers[id];
     const size_t bytes = (size_t)h->npc*h->npc*h->stride*sizeof(double);
     if (!t.bc_value_f) {
-        HIP_TRY(h, hipMalloc(&t.bc_value_f, bytes));
+        HIP_TRY(h, t.bc_value_f.alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(t.bc_value_f, 0, bytes, h->stream));
     }
     return scatter_facet_values(h, t.bc_value_f, n_facets, cells, facets, values, 1, h->npc);
@@ -334,7 +330,7 @@ int swe2d_tracer_set_bc_field(swe2d_handle *hh, int id, int marker, const double
     Handle::Tracer &t = h->tracers[id];
     const size_t bytes = (size_t)h->npc*h->npc*h->stride*sizeof(double);
     if (!t.bc_value_f) {
-        HIP_TRY(h, hipMalloc(&t.bc_value_f, bytes));
+        HIP_TRY(h, t.bc_value_f.alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(t.bc_value_f, 0, bytes, h->stream));
     }
     HIP_TRY(h, hipMemcpyAsync(h->stage_eta, nodal, (size_t)h->npc*h->n_cells*sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -359,10 +355,10 @@ int swe2d_tracer_set_source(swe2d_handle *hh, int id, const double *nodal)
     }
     t.rx.n_code = 0;                                    // (an uploaded source replaces a reaction program)
     if (!nodal) {
-        if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }
+        if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); t.source.reset(); }
         return SWE2D_OK;
     }
-    if (!t.source) HIP_TRY(h, hipMalloc(&t.source, (size_t)h->npc*h->stride*sizeof(double)));
+    HIP_TRY(h, t.source.ensure((size_t)h->npc*h->stride));
     HIP_TRY(h, hipMemcpyAsync(h->stage_eta, nodal, (size_t)h->npc*h->n_cells*sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(swe_nodal_to_planes, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream,
                        h->stage_eta, t.source, h->stride, h->n_cells, 1, h->npc);
@@ -414,7 +410,7 @@ int swe2d_tracer_set_diffusivity(swe2d_handle *hh, int id, int enable, const dou
     if (!enable) { t.diff = false; return SWE2D_OK; }
     if (!mu_vertex && !(mu_const >= 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "diffusivity must be >= 0");
     if (!(sipg_factor_tracer > 0.0)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "sipg_factor_tracer must be > 0");
-    rc = upload_vertex_coefficient(h, mu_vertex, &t.mu_v);
+    rc = upload_vertex_coefficient(h, mu_vertex, t.mu_v);
     if (rc) return rc;
     t.mu_const = mu_const;
     t.sipg_factor = sipg_factor_tracer;

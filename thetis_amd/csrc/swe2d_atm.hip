@@ -90,23 +90,16 @@ int atm_outside(Handle *h, const char *who, double t)
     return fail(h, SWE2D_ERR_INVALID_ARGUMENT, buf);
 }
 
-// hipMalloc whose failure names the bytes asked for
-int atm_alloc(Handle *h, double **p, size_t bytes, const char *what)
+// an allocation whose failure names the bytes asked for
+int atm_alloc(Handle *h, DevArray<double> &p, size_t bytes, const char *what)
 {
-    const hipError_t e = hipMalloc(p, bytes);
+    const hipError_t e = p.alloc(bytes/sizeof(double));
     if (e == hipSuccess) return SWE2D_OK;
     (void)hipGetLastError();
-    *p = nullptr;
     return fail(h, SWE2D_ERR_HIP, std::string("swe2d_atm_set: ") + std::to_string(bytes) + " bytes of " + what + ": " + hipGetErrorString(e));
 }
 
 }  // namespace
-
-void swe2d_impl::atm_free(Handle *h)
-{
-    if (h->atm.tab) (void)hipFree(h->atm.tab);
-    h->atm = Handle::Atm();
-}
 
 int swe2d_impl::atm_launch(Handle *h, double t)
 {
@@ -175,12 +168,12 @@ int swe2d_atm_set(swe2d_handle *hh, int32_t n_times, const double *times, const 
         }
     for (double x : host) if (!std::isfinite(x)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_atm_set: the tables must be finite");
     HIP_TRY(h, hipSetDevice(h->device));
-    // build aside: the table and whatever field planes are absent; a failure frees them and leaves the handle as it was
-    double *tab = nullptr, *wind = nullptr, *patm = nullptr;
+    // build aside: the table and whatever field planes are absent; a failure leaves the handle as it was
+    DevArray<double> tab, wind, patm;
     const size_t plane_bytes = (size_t)h->npc*h->stride*sizeof(double);
-    int rc = atm_alloc(h, &tab, host.size()*sizeof(double), "atmospheric record");
-    if (!rc && (which & 1) && !h->field[SWE2D_FIELD_WIND_STRESS]) rc = atm_alloc(h, &wind, 2*plane_bytes, "wind stress planes");
-    if (!rc && (which & 2) && !h->field[SWE2D_FIELD_ATMOSPHERIC_PRESSURE]) rc = atm_alloc(h, &patm, plane_bytes, "pressure planes");
+    int rc = atm_alloc(h, tab, host.size()*sizeof(double), "atmospheric record");
+    if (!rc && (which & 1) && !h->field[SWE2D_FIELD_WIND_STRESS]) rc = atm_alloc(h, wind, 2*plane_bytes, "wind stress planes");
+    if (!rc && (which & 2) && !h->field[SWE2D_FIELD_ATMOSPHERIC_PRESSURE]) rc = atm_alloc(h, patm, plane_bytes, "pressure planes");
     hipError_t e = hipSuccess;
     if (!rc) e = hipStreamSynchronize(h->stream);                         // launches that read the old table are done
     if (!rc && e == hipSuccess) e = hipMemcpyAsync(tab, host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, h->stream);
@@ -191,18 +184,12 @@ int swe2d_atm_set(swe2d_handle *hh, int32_t n_times, const double *times, const 
         (void)hipGetLastError();
         rc = fail(h, SWE2D_ERR_HIP, std::string("swe2d_atm_set: ") + hipGetErrorString(e));
     }
-    if (rc) {
-        if (tab) (void)hipFree(tab);
-        if (wind) (void)hipFree(wind);
-        if (patm) (void)hipFree(patm);
-        return rc;
-    }
-    // swap in
-    if (h->atm.tab) (void)hipFree(h->atm.tab);
-    if (wind) h->field[SWE2D_FIELD_WIND_STRESS] = wind;
-    if (patm) h->field[SWE2D_FIELD_ATMOSPHERIC_PRESSURE] = patm;
+    if (rc) return rc;
+    // move in
+    if (wind) h->field[SWE2D_FIELD_WIND_STRESS] = std::move(wind);
+    if (patm) h->field[SWE2D_FIELD_ATMOSPHERIC_PRESSURE] = std::move(patm);
     Handle::Atm &am = h->atm;
-    am.tab = tab;
+    am.tab = std::move(tab);
     am.times.assign(times, times + nt);
     am.which = which; am.method = method; am.W = (int)W;
     am.n_t = n_times;                                                     // from here on the handle has a record (step_kernels)
@@ -217,7 +204,7 @@ int swe2d_atm_clear(swe2d_handle *hh)
     if (h->atm.n_t == 0) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    atm_free(h);
+    h->atm = Handle::Atm();
     return SWE2D_OK;
 }
 

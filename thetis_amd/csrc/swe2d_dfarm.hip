@@ -322,7 +322,7 @@ void dfarm_fill(Handle *h, const Handle::Farm &f, int m, SweDfarmRule &R, SweDfa
     std::memcpy(R.w, f.w, sizeof(R.w));
     R.n_q = f.n_q;
     a = SweDfarmArgs{};
-    a.F = &h->farm_table->f[m];
+    a.F = &h->farm_table.get()->f[m];
     a.stride = (unsigned)h->stride;
     a.cells = f.cells; a.dtab = f.dtab; a.n_list = f.n_list;
     a.cv = h->cv; a.vx = h->vx; a.vy = h->vy; a.vh = h->vh;
@@ -331,12 +331,6 @@ void dfarm_fill(Handle *h, const Handle::Farm &f, int m, SweDfarmRule &R, SweDfa
 
 // the instance of a kernel template <NPC, AFFINE> for the handle's cells
 #define DFARM_PICK(h, kern) ((h)->npc == 3 ? kern<3, true> : ((h)->affine ? kern<4, true> : kern<4, false>))
-
-// a slot under construction: released unless it is handed over
-struct FarmGuard {
-    Handle::Farm f;
-    ~FarmGuard() { farm_release(f); }
-};
 
 }  // namespace
 
@@ -442,29 +436,28 @@ int swe2d_dfarm_set(swe2d_handle *hh, int32_t farm, const swe2d_turbine_params *
             for (int j = c_off[c]; j < c_off[c + 1]; j++) t_pos[fill[c_idx[j]]++] = c;
     }
     // ---- the new slot, built aside: a failure leaves the handle as it was
-    FarmGuard g;
-    Handle::Farm &f = g.f;
+    Handle::Farm f;
     f.discrete = true;
     f.par = *p;
     f.n_q = n_q; f.n_turbines = n_turbines; f.radius = r; f.n_list = n_list; f.nnz = nnz;
     std::memcpy(f.phi, phi, (size_t)n_q*npc*sizeof(double));
     std::memcpy(f.w, w, (size_t)n_q*sizeof(double));
     if (n_turbines > 0) {
-        HIP_TRY(h, hipMalloc(&f.txy, (size_t)2*n_turbines*sizeof(double)));
+        HIP_TRY(h, f.txy.alloc((size_t)2*n_turbines));
         HIP_TRY(h, hipMemcpy(f.txy, xy, (size_t)2*n_turbines*sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(&f.tpow, (size_t)n_turbines*(SWE_SUM_LIMBS + 1)*sizeof(unsigned long long)));
+        HIP_TRY(h, f.tpow.alloc((size_t)n_turbines*(SWE_SUM_LIMBS + 1)));
     }
     if (n_list > 0) {
-        HIP_TRY(h, hipMalloc(&f.cells, (size_t)n_list*sizeof(int)));
+        HIP_TRY(h, f.cells.alloc(n_list));
         HIP_TRY(h, hipMemcpy(f.cells, list.data(), (size_t)n_list*sizeof(int), hipMemcpyHostToDevice));
         const size_t n_int = (size_t)n_list + 1 + nnz + n_turbines + 1 + nnz;
-        HIP_TRY(h, hipMalloc(&f.csr, n_int*sizeof(int)));
+        HIP_TRY(h, f.csr.alloc(n_int));
         int *d = f.csr;
         HIP_TRY(h, hipMemcpy(d, c_off.data(), ((size_t)n_list + 1)*sizeof(int), hipMemcpyHostToDevice)); d += n_list + 1;
         HIP_TRY(h, hipMemcpy(d, c_idx.data(), (size_t)nnz*sizeof(int), hipMemcpyHostToDevice)); d += nnz;
         HIP_TRY(h, hipMemcpy(d, t_off.data(), ((size_t)n_turbines + 1)*sizeof(int), hipMemcpyHostToDevice)); d += n_turbines + 1;
         HIP_TRY(h, hipMemcpy(d, t_pos.data(), (size_t)nnz*sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(&f.dtab, (size_t)n_q*n_list*sizeof(double)));
+        HIP_TRY(h, f.dtab.alloc((size_t)n_q*n_list));
         SweDfarmRule R;
         std::memcpy(R.phi, f.phi, sizeof(R.phi));
         std::memcpy(R.w, f.w, sizeof(R.w));
@@ -481,9 +474,8 @@ int swe2d_dfarm_set(swe2d_handle *hh, int32_t farm, const swe2d_turbine_params *
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (!h->farm_rows) { if (int rc = farm_rows_alloc(h, 0)) return rc; }
-    if (!h->farm_table) HIP_TRY(h, hipMalloc(&h->farm_table, sizeof(SweFarmTable)));
     f.live = true;
-    std::swap(h->farms[farm], f);                                         // the guard releases what the slot held
+    std::swap(h->farms[farm], f);                                         // `f` takes what the slot held with it
     return farm_upload_table(h);
 }
 

@@ -278,17 +278,6 @@ int particles_check(Handle *h, int id, Handle::Particles **out)
     return SWE2D_OK;
 }
 
-void particles_release(Handle::Particles &s)
-{
-    if (s.pos) (void)hipFree(s.pos);
-    if (s.ist) (void)hipFree(s.ist);
-    if (s.out) (void)hipFree(s.out);
-    if (s.release) (void)hipFree(s.release);
-    if (s.kv) (void)hipFree(s.kv);
-    if (s.counts) (void)hipFree(s.counts);
-    s = Handle::Particles();
-}
-
 // the bit mask of the open markers of an advance, or false (the handle has the message)
 bool particles_open_mask(Handle *h, int n_open, const int32_t *open_markers, double dt_move, const char *who, unsigned *mask)
 {
@@ -322,12 +311,6 @@ SweParticleArgs particles_args(const Handle *h, const Handle::Particles *s, doub
 
 }  // namespace
 
-void swe2d_impl::particles_free_all(Handle *h)
-{
-    for (auto &s : h->particles) particles_release(s);
-    h->particles.clear();
-}
-
 int swe2d_particles_create(swe2d_handle *hh, int32_t n, const double *xy, const int32_t *cells, int32_t capacity, int32_t *particles_id)
 {
     Handle *h = H(hh);
@@ -354,30 +337,17 @@ int swe2d_particles_create(swe2d_handle *hh, int32_t n, const double *xy, const 
     }
     Handle::Particles s;
     s.n = n; s.capacity = capacity;
-    const size_t pos_bytes = (size_t)n*2*sizeof(double), ist_bytes = (size_t)n*4*sizeof(int),
-                 out_bytes = (size_t)std::max(capacity, 1)*pos_bytes;
-    hipError_t e = hipMalloc(&s.pos, pos_bytes);
-    if (e == hipSuccess) e = hipMalloc(&s.ist, ist_bytes);
-    if (e == hipSuccess) e = hipMalloc(&s.out, out_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        particles_release(s);
-        return fail(h, SWE2D_ERR_HIP, "swe2d_particles_create: " + std::to_string(pos_bytes + ist_bytes + out_bytes)
-                    + " bytes of particle state and rows: " + hipGetErrorString(e));
-    }
-    e = hipMemcpyAsync(s.pos, xy, pos_bytes, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.ist, 0, ist_bytes, h->stream);       // ACTIVE, no marker, no hits
-    if (e == hipSuccess) e = hipMemcpyAsync(s.ist, cells, (size_t)n*sizeof(int), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);                      // the host arrays may be reused by the caller
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        particles_release(s);
-        return fail(h, SWE2D_ERR_HIP, std::string("swe2d_particles_create: ") + hipGetErrorString(e));
-    }
+    HIP_TRY(h, s.pos.alloc((size_t)n*2));
+    HIP_TRY(h, s.ist.alloc((size_t)n*4));
+    HIP_TRY(h, s.out.alloc((size_t)std::max(capacity, 1)*n*2));
+    HIP_TRY(h, hipMemcpyAsync(s.pos, xy, (size_t)n*2*sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(s.ist, 0, (size_t)n*4*sizeof(int), h->stream));         // ACTIVE, no marker, no hits
+    HIP_TRY(h, hipMemcpyAsync(s.ist, cells, (size_t)n*sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                                   // the host arrays may be reused by the caller
     s.live = true;
     int id = 0;
     while (id < (int)h->particles.size() && h->particles[id].live) id++;
-    if (id == (int)h->particles.size()) h->particles.push_back(s); else h->particles[id] = s;
+    if (id == (int)h->particles.size()) h->particles.push_back(std::move(s)); else h->particles[id] = std::move(s);
     *particles_id = id;
     return SWE2D_OK;
 }
@@ -410,14 +380,7 @@ int swe2d_particles_set_diffusivity(swe2d_handle *hh, int32_t id, int32_t n_vert
             return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_diffusivity: the diffusivity must be finite and not negative");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)n_vertices*sizeof(double);
-    if (!s->kv) {
-        const hipError_t e = hipMalloc(&s->kv, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            s->kv = nullptr;
-            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_set_diffusivity: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-        }
-    }
+    HIP_TRY(h, s->kv.ensure(n_vertices));
     HIP_TRY(h, hipMemcpyAsync(s->kv, diffusivity, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                           // the host array may be reused by the caller
     s->seed = seed;
@@ -437,14 +400,7 @@ int swe2d_particles_set_release_times(swe2d_handle *hh, int32_t id, int32_t n, c
             return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_particles_set_release_times: a release time is not a number");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)n*sizeof(double);
-    if (!s->release) {
-        const hipError_t e = hipMalloc(&s->release, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            s->release = nullptr;
-            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_set_release_times: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-        }
-    }
+    HIP_TRY(h, s->release.ensure(n));
     // ACTIVE <-> WAITING by the new times; EXITED and LOST particles stay what they are
     std::vector<int> status((size_t)n);
     HIP_TRY(h, hipMemcpyAsync(status.data(), s->ist + (size_t)n, (size_t)n*sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -496,14 +452,7 @@ int swe2d_particles_cell_counts(swe2d_handle *hh, int32_t id, uint32_t status_ma
     if (!counts) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)h->n_cells*sizeof(int);
-    if (!s->counts) {
-        const hipError_t e = hipMalloc(&s->counts, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            s->counts = nullptr;
-            return fail(h, SWE2D_ERR_HIP, "swe2d_particles_cell_counts: " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-        }
-    }
+    HIP_TRY(h, s->counts.ensure(h->n_cells));
     HIP_TRY(h, hipMemsetAsync(s->counts, 0, bytes, h->stream));
     hipLaunchKernelGGL(swe_particle_count_kernel, dim3((unsigned)grid_for(s->n)), dim3(256), 0, h->stream, s->ist, s->n, status_mask,
                        h->n_cells, s->counts);
@@ -566,6 +515,6 @@ int swe2d_particles_destroy(swe2d_handle *hh, int32_t id)
     if (int rc = particles_check(h, id, &s)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                           // moves may still be in flight
-    particles_release(*s);
+    *s = Handle::Particles();
     return SWE2D_OK;
 }

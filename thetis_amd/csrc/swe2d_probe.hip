@@ -78,14 +78,6 @@ int probe_check(Handle *h, int id, Handle::Probe **out)
     return SWE2D_OK;
 }
 
-void probe_release(Handle::Probe &p)
-{
-    if (p.cell) (void)hipFree(p.cell);
-    if (p.weight) (void)hipFree(p.weight);
-    if (p.out) (void)hipFree(p.out);
-    p = Handle::Probe();
-}
-
 int launch_probe(Handle *h, const Handle::Probe &p, int row)
 {
     SweProbeArgs a{};
@@ -115,12 +107,6 @@ int launch_probe(Handle *h, const Handle::Probe &p, int row)
 
 }  // namespace
 
-void swe2d_impl::probe_free_all(Handle *h)
-{
-    for (auto &p : h->probes) probe_release(p);
-    h->probes.clear();
-}
-
 int swe2d_probe_create(swe2d_handle *hh, int32_t n_points, const int32_t *cells, const double *weights, int32_t n_fields,
                        const int32_t *fields, int32_t capacity, int32_t *probe_id)
 {
@@ -147,21 +133,16 @@ int swe2d_probe_create(swe2d_handle *hh, int32_t n_points, const int32_t *cells,
     Handle::Probe p;
     p.n_points = n_points; p.width = width; p.capacity = capacity;
     p.fields.assign(fields, fields + n_fields);
-    hipError_t e = hipMalloc(&p.cell, (size_t)n_points*sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&p.weight, (size_t)n_points*h->npc*sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&p.out, ((size_t)capacity + 1)*row_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(p.cell, cells, (size_t)n_points*sizeof(int), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p.weight, weights, (size_t)n_points*h->npc*sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);             // the host arrays may be reused by the caller
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        probe_release(p);
-        return fail(h, SWE2D_ERR_HIP, std::string("swe2d_probe_create: ") + hipGetErrorString(e));
-    }
+    HIP_TRY(h, p.cell.alloc(n_points));
+    HIP_TRY(h, p.weight.alloc((size_t)n_points*h->npc));
+    HIP_TRY(h, p.out.alloc(((size_t)capacity + 1)*n_points*width));
+    HIP_TRY(h, hipMemcpyAsync(p.cell, cells, (size_t)n_points*sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(p.weight, weights, (size_t)n_points*h->npc*sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                          // the host arrays may be reused by the caller
     p.live = true;
     int id = 0;
     while (id < (int)h->probes.size() && h->probes[id].live) id++;
-    if (id == (int)h->probes.size()) h->probes.push_back(p); else h->probes[id] = p;
+    if (id == (int)h->probes.size()) h->probes.push_back(std::move(p)); else h->probes[id] = std::move(p);
     *probe_id = id;
     return SWE2D_OK;
 }
@@ -227,6 +208,6 @@ int swe2d_probe_destroy(swe2d_handle *hh, int32_t id)
     if (int rc = probe_check(h, id, &p)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                           // rows may still be in flight
-    probe_release(*p);
+    *p = Handle::Probe();
     return SWE2D_OK;
 }

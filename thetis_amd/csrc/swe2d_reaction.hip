@@ -181,12 +181,6 @@ int swe2d_impl::reaction_launch(Handle *h, int id, int in, int c0, int c1)
     return SWE2D_OK;
 }
 
-void swe2d_impl::reaction_free_all(Handle *h)
-{
-    for (int f = 0; f < SWE2D_REACTION_MAX_FIELDS; f++)
-        if (h->rx_field[f]) { (void)hipFree(h->rx_field[f]); h->rx_field[f] = nullptr; }
-}
-
 extern "C" {
 
 int swe2d_tracer_set_reaction(swe2d_handle *hh, int id, int32_t n_code, const int32_t *code, int32_t n_const, const double *consts,
@@ -200,7 +194,7 @@ int swe2d_tracer_set_reaction(swe2d_handle *hh, int id, int32_t n_code, const in
         return n_code == 0 ? SWE2D_OK : fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tracer_set_reaction: the sediment field's source comes from the sediment model (swe2d_sediment_clear first)");
     if (n_code == 0) {                                                      // no program, no source
         t.rx.n_code = 0;
-        if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }
+        if (t.source) { HIP_TRY(h, hipStreamSynchronize(h->stream)); t.source.reset(); }
         return SWE2D_OK;
     }
     if (h->npc == 4 && !h->affine)
@@ -264,12 +258,7 @@ int swe2d_tracer_set_reaction(swe2d_handle *hh, int id, int32_t n_code, const in
     std::memcpy(rx.w, w, (size_t)n_q*sizeof(double));
     if (!t.source) {
         const size_t bytes = (size_t)h->npc*h->stride*sizeof(double);
-        const hipError_t e = hipMalloc(&t.source, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            t.source = nullptr;
-            return fail(h, SWE2D_ERR_HIP, "swe2d_tracer_set_reaction: " + std::to_string(bytes) + " bytes of source planes: " + hipGetErrorString(e));
-        }
+        HIP_TRY(h, t.source.alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(t.source, 0, bytes, h->stream));
     }
     t.rx = rx;
@@ -295,17 +284,12 @@ int swe2d_reaction_set_field(swe2d_handle *hh, int32_t slot, const double *nodal
     if (slot < 0 || slot >= SWE2D_REACTION_MAX_FIELDS) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_reaction_set_field: slot out of range");
     HIP_TRY(h, hipSetDevice(h->device));
     if (!nodal) {
-        if (h->rx_field[slot]) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(h->rx_field[slot])); h->rx_field[slot] = nullptr; }
+        if (h->rx_field[slot]) { HIP_TRY(h, hipStreamSynchronize(h->stream)); h->rx_field[slot].reset(); }
         return SWE2D_OK;
     }
     if (!h->rx_field[slot]) {
         const size_t bytes = (size_t)h->npc*h->stride*sizeof(double);
-        const hipError_t e = hipMalloc(&h->rx_field[slot], bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            h->rx_field[slot] = nullptr;
-            return fail(h, SWE2D_ERR_HIP, "swe2d_reaction_set_field: " + std::to_string(bytes) + " bytes of coefficient planes: " + hipGetErrorString(e));
-        }
+        HIP_TRY(h, h->rx_field[slot].alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(h->rx_field[slot], 0, bytes, h->stream));          // (the planes' padding beyond n_cells)
     }
     HIP_TRY(h, hipMemcpyAsync(h->stage_eta, nodal, (size_t)h->npc*h->n_cells*sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -92,21 +92,11 @@ __global__ void __launch_bounds__(SWE_BLOCK) swe_section_transport_kernel(SweSec
 
 namespace {
 
-void sections_release(Handle *h)
+int sections_rows_alloc(Handle *h, Handle::Sections &s, int capacity)
 {
-    Handle::Sections &s = h->sections;
-    if (s.cell) (void)hipFree(s.cell);
-    if (s.geom) (void)hipFree(s.geom);
-    if (s.rows) (void)hipFree(s.rows);
-    s = Handle::Sections();
-}
-
-int sections_rows_alloc(Handle *h, int capacity)
-{
-    Handle::Sections &s = h->sections;
     if (s.rows && s.rows_cap == capacity) return SWE2D_OK;
-    if (s.rows) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(s.rows)); s.rows = nullptr; }
-    HIP_TRY(h, hipMalloc(&s.rows, ((size_t)capacity + 1)*SWE_SECTION_ROW*sizeof(unsigned long long)));
+    if (s.rows) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, s.rows.alloc(((size_t)capacity + 1)*SWE_SECTION_ROW));
     s.rows_cap = capacity;
     s.rows_n = 0;
     return SWE2D_OK;
@@ -157,8 +147,6 @@ void row_to_values(const unsigned long long *row, double *values)
 }
 
 }  // namespace
-
-void swe2d_impl::sections_free(Handle *h) { sections_release(h); }
 
 extern "C" {
 
@@ -215,27 +203,18 @@ int swe2d_sections_set(swe2d_handle *hh, int32_t n_sections, int32_t n_pieces, c
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                          // launches that read the old tables are done
-    sections_release(h);
-    Handle::Sections &s = h->sections;
-    s = fresh;
+    h->sections = Handle::Sections();                                     // (a failure below leaves the handle without sections)
+    Handle::Sections &s = fresh;
     s.n_tracers = n_tracers;
     for (int m = 0; m < n_tracers; m++) s.tracer_ids[m] = tracer_ids[m];
-    auto undo = [&](int rc) { sections_release(h); return rc; };
-    if (hipMalloc(&s.cell, cell.size()*sizeof(int)) != hipSuccess || hipMalloc(&s.geom, geom.size()*sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(h, SWE2D_ERR_HIP, "swe2d_sections_set: out of device memory"));
-    }
-    if (hipMemcpy(s.cell, cell.data(), cell.size()*sizeof(int), hipMemcpyHostToDevice) != hipSuccess
-        || hipMemcpy(s.geom, geom.data(), geom.size()*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(h, SWE2D_ERR_HIP, "swe2d_sections_set: upload failed"));
-    }
+    HIP_TRY(h, s.cell.alloc(cell.size()));
+    HIP_TRY(h, s.geom.alloc(geom.size()));
+    HIP_TRY(h, hipMemcpy(s.cell, cell.data(), cell.size()*sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(s.geom, geom.data(), geom.size()*sizeof(double), hipMemcpyHostToDevice));
     s.n_lanes = n_lanes;
-    if (int rc = sections_rows_alloc(h, 0)) return undo(rc);
-    if (hipMemsetAsync(s.rows, 0, SWE_SECTION_ROW*sizeof(unsigned long long), h->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(h, SWE2D_ERR_HIP, "swe2d_sections_set: clearing the row store failed"));
-    }
+    if (int rc = sections_rows_alloc(h, s, 0)) return rc;
+    HIP_TRY(h, hipMemsetAsync(s.rows, 0, SWE_SECTION_ROW*sizeof(unsigned long long), h->stream));
+    h->sections = std::move(fresh);
     return SWE2D_OK;
 }
 
@@ -246,7 +225,7 @@ int swe2d_sections_clear(swe2d_handle *hh)
     if (h->sections.n_lanes == 0) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    sections_release(h);
+    h->sections = Handle::Sections();
     return SWE2D_OK;
 }
 
@@ -287,7 +266,7 @@ int swe2d_sections_rows_reserve(swe2d_handle *hh, int32_t capacity)
     if (int rc = sections_check(h, true)) return rc;
     if (capacity < 0 || capacity > (1 << 20)) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_sections_rows_reserve: bad capacity");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = sections_rows_alloc(h, capacity)) return rc;
+    if (int rc = sections_rows_alloc(h, h->sections, capacity)) return rc;
     h->sections.rows_n = 0;
     HIP_TRY(h, hipMemsetAsync(h->sections.rows, 0, ((size_t)capacity + 1)*SWE_SECTION_ROW*sizeof(unsigned long long), h->stream));
     return SWE2D_OK;

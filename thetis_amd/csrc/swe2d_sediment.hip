@@ -453,25 +453,11 @@ void sediment_fill(Handle *h, SweSedArgs &a)
     a.par = h->sed.par;
 }
 
-void sediment_release_tables(Handle *h)
+// after a model was switched off: the shared tables go with the last model that reads them
+void exner_release_unused(Handle *h)
 {
-    Handle::Sediment &s = h->sed;
-    void *ptrs[] = {s.v_off, s.v_ent, s.area, s.vh_new, s.count};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    s.v_off = s.v_ent = nullptr; s.area = s.vh_new = nullptr; s.count = nullptr;
-}
-
-void sediment_release(Handle *h)
-{
-    Handle::Sediment &s = h->sed;
-    if (s.planes) (void)hipFree(s.planes);
-    Handle::Sediment none;
-    if (h->bed.on || h->slide.on) {                     // the bedload model and the slide go on reading the Exner tables
-        none.v_off = s.v_off; none.v_ent = s.v_ent; none.area = s.area; none.vh_new = s.vh_new; none.count = s.count;
-    } else {
-        sediment_release_tables(h);
-    }
-    s = none;
+    if (!h->sed.on && !h->bed.on && !h->slide.on) h->exner = Handle::Exner();
+    if (!h->bed.on && !h->slide.on) h->exner_grad.reset();
 }
 
 // triangle areas as HostSediment forms them: 0.5*|(x1 - x0)*(y2 - y0) - (x2 - x0)*(y1 - y0)|, no contraction
@@ -488,13 +474,13 @@ void sediment_areas(const Handle *h, const double *vx, const double *vy, std::ve
     }
 }
 
-// the Exner tables (vertex lists, areas, the second bed array, the counter), shared by the sediment field and the bedload model
-int exner_tables_build(Handle *h, const char *who)
+// the Exner tables (vertex lists, areas, the second bed array, the counter), shared by the sediment field, the bedload model and
+// the slide: built aside and moved into place whole
+int exner_tables_build(Handle *h)
 {
-    Handle::Sediment &s = h->sed;
     const int n = h->n_cells, nv = h->n_vertices;
-    if (!s.count) {                                    // (count is allocated last: a failed attempt is released and built again)
-        sediment_release_tables(h);
+    if (!h->exner.count) {
+        Handle::Exner s;
         // vertex -> (cell, local node), cells ascending; triangle areas
         std::vector<int> off(nv + 1, 0);
         for (size_t j = 0; j < (size_t)3*n; j++) off[h->host_cells[j] + 1]++;
@@ -506,17 +492,16 @@ int exner_tables_build(Handle *h, const char *who)
         HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
         HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
         sediment_areas(h, vx.data(), vy.data(), area);
-        HIP_TRY(h, hipMalloc(&s.v_off, off.size()*sizeof(int)));
-        HIP_TRY(h, hipMalloc(&s.v_ent, ent.size()*sizeof(int)));
-        HIP_TRY(h, hipMalloc(&s.area, (size_t)n*sizeof(double)));
-        HIP_TRY(h, hipMalloc(&s.vh_new, (size_t)nv*sizeof(double)));
+        HIP_TRY(h, s.v_off.alloc(off.size()));
+        HIP_TRY(h, s.v_ent.alloc(ent.size()));
+        HIP_TRY(h, s.area.alloc(n));
+        HIP_TRY(h, s.vh_new.alloc(nv));
         HIP_TRY(h, hipMemcpy(s.v_off, off.data(), off.size()*sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(s.v_ent, ent.data(), ent.size()*sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(s.area, area.data(), (size_t)n*sizeof(double), hipMemcpyHostToDevice));
-        unsigned *cnt = nullptr;
-        HIP_TRY(h, hipMalloc(&cnt, sizeof(unsigned)));
-        if (hipMemset(cnt, 0, sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(cnt); return fail(h, SWE2D_ERR_HIP, (std::string(who) + ": clearing the counter failed").c_str()); }
-        s.count = cnt;
+        HIP_TRY(h, s.count.alloc(1));
+        HIP_TRY(h, hipMemset(s.count, 0, sizeof(unsigned)));
+        h->exner = std::move(s);
     }
     return SWE2D_OK;
 }
@@ -538,42 +523,20 @@ void bedload_gradients(const Handle *h, const double *vx, const double *vy, std:
     }
 }
 
-void bedload_release(Handle *h)
+// the gradient table of the bedload pass and the slide, built by whichever comes first
+int gradient_table_build(Handle *h)
 {
-    Handle::Bedload &b = h->bed;
-    if (b.planes) (void)hipFree(b.planes);
-    Handle::Bedload none;
-    if (h->slide.on) none.grad = b.grad;                // the slide goes on reading the gradient table
-    else if (b.grad) (void)hipFree(b.grad);
-    b = none;
-}
-
-void slide_release(Handle *h)
-{
-    Handle::Slide &s = h->slide;
-    void *ptrs[] = {s.planes, s.region, s.words};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    s = Handle::Slide();
-    if (!h->bed.on && h->bed.grad) { (void)hipFree(h->bed.grad); h->bed.grad = nullptr; }
-}
-
-// the gradient table of the bedload pass and the slide (kept with the bedload model, built by whichever comes first)
-int gradient_table_build(Handle *h, const char *who)
-{
-    if (h->bed.grad) return SWE2D_OK;
+    if (h->exner_grad) return SWE2D_OK;
     const size_t S = h->stride;
     const int nv = h->n_vertices;
     std::vector<double> vx(nv), vy(nv), grad;
     HIP_TRY(h, hipMemcpy(vx.data(), h->vx, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(vy.data(), h->vy, (size_t)nv*sizeof(double), hipMemcpyDeviceToHost));
     bedload_gradients(h, vx.data(), vy.data(), grad);
-    double *g = nullptr;
-    HIP_TRY(h, hipMalloc(&g, 6*S*sizeof(double)));
-    if (hipMemcpy(g, grad.data(), 6*S*sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(g);
-        return fail(h, SWE2D_ERR_HIP, (std::string(who) + ": uploading the gradient table failed").c_str());
-    }
-    h->bed.grad = g;
+    DevArray<double> g;
+    HIP_TRY(h, g.alloc(6*S));
+    HIP_TRY(h, hipMemcpy(g, grad.data(), 6*S*sizeof(double), hipMemcpyHostToDevice));
+    h->exner_grad = std::move(g);
     return SWE2D_OK;
 }
 
@@ -643,12 +606,13 @@ int swe2d_impl::sediment_update_launch(Handle *h)
 int swe2d_impl::exner_launch(Handle *h)
 {
     Handle::Sediment &s = h->sed;
+    const Handle::Exner &x = h->exner;
     SweSedArgs a{};
     sediment_fill(h, a);
-    a.tin = s.on ? h->tracers[s.tracer].buf[0] : nullptr;
-    a.list = s.v_off; a.ent = s.v_ent; a.area = s.area;
-    a.out = s.vh_new;
-    a.count = s.count;
+    a.tin = s.on ? h->tracers[s.tracer].buf[0].get() : nullptr;
+    a.list = x.v_off; a.ent = x.v_ent; a.area = x.area;
+    a.out = x.vh_new;
+    a.count = x.count;
     a.begin = 0; a.end = h->n_vertices;
     // (a handle without a sediment field takes the factor and the floor from the bedload parameters, one with the slide alone from its)
     a.dtf = h->par.dt*(s.on ? s.par.fac : (h->bed.on ? h->bed.par.fac : h->slide.par.fac));
@@ -668,18 +632,16 @@ int swe2d_impl::exner_launch(Handle *h)
     default: hipLaunchKernelGGL((swe_exner_kernel<true, true, true>), grid, block, 0, h->stream, a); break;
     }
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->vh, s.vh_new, (size_t)h->n_vertices*sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->vh, x.vh_new, (size_t)h->n_vertices*sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SWE2D_OK;
 }
-
-void swe2d_impl::sediment_free(Handle *h) { slide_release(h); bedload_release(h); sediment_release(h); }
 
 int swe2d_impl::slide_update_launch(Handle *h)
 {
     Handle::Slide &sl = h->slide;
     SweSlideArgs a{};
     a.cv = h->cv; a.vh = h->vh;
-    a.grad = h->bed.grad; a.area = h->sed.area; a.region = sl.region;
+    a.grad = h->exner_grad; a.area = h->exner.area; a.region = sl.region;
     a.planes = sl.planes; a.words = sl.words;
     a.stride = h->stride;
     a.n_cells = h->n_cells;
@@ -717,7 +679,7 @@ int bedload_launch(Handle *h, bool with_coefficients)
     SweBedArgs a{};
     a.state = h->state[0];
     a.cv = h->cv; a.nbr = h->nbr; a.vh = h->vh;
-    a.grad = b.grad; a.area = h->sed.area; a.planes = b.planes;
+    a.grad = h->exner_grad; a.area = h->exner.area; a.planes = b.planes;
     a.stride = h->stride;
     a.n_cells = h->n_cells;
     a.nonlinear = h->par.use_nonlinear_equations ? 1 : 0;
@@ -769,16 +731,16 @@ int swe2d_sediment_set(swe2d_handle *hh, int tracer_id, const swe2d_sediment_par
     Handle::Sediment &s = h->sed;
     const size_t S = h->stride, plane_bytes = 3*S*sizeof(double);
     if (!s.planes) {
-        HIP_TRY(h, hipMalloc(&s.planes, 3*plane_bytes));
+        HIP_TRY(h, s.planes.alloc(9*S));
         HIP_TRY(h, hipMemsetAsync(s.planes, 0, 3*plane_bytes, h->stream));
     }
     if (!s.on && (t.source || t.rx.n_code > 0))
         return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_sediment_set: the tracer has a source or a reaction program already (remove it first)");
     if (!t.source) {
-        HIP_TRY(h, hipMalloc(&t.source, plane_bytes));
+        HIP_TRY(h, t.source.alloc(plane_bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(t.source, 0, plane_bytes, h->stream));
     }
-    if (int rc = exner_tables_build(h, "swe2d_sediment_set")) return rc;
+    if (int rc = exner_tables_build(h)) return rc;
     s.par = *par;
     s.tracer = tracer_id;
     s.on = true;
@@ -796,7 +758,7 @@ int swe2d_sediment_set_equilibrium_bc(swe2d_handle *hh, int marker, int on)
     if (on) {
         if (!t.bc_value_f) {
             const size_t bytes = (size_t)9*h->stride*sizeof(double);
-            HIP_TRY(h, hipMalloc(&t.bc_value_f, bytes));
+            HIP_TRY(h, t.bc_value_f.alloc(bytes/sizeof(double)));
             HIP_TRY(h, hipMemsetAsync(t.bc_value_f, 0, bytes, h->stream));
         }
         h->sed.eq_markers |= 1u << marker;
@@ -862,9 +824,10 @@ int swe2d_sediment_clear(swe2d_handle *hh)
     Handle::Tracer &t = h->tracers[h->sed.tracer];
     for (int m = 1; m < SWE2D_MAX_MARKERS; m++)
         if ((h->sed.eq_markers >> m) & 1u) t.bc_has_value[m] = 0;
-    if (t.source) { HIP_TRY(h, hipFree(t.source)); t.source = nullptr; }       // (allocated by swe2d_sediment_set: it refuses a tracer with one)
+    t.source.reset();       // (allocated by swe2d_sediment_set: it refuses a tracer with one)
     t.conservative = false;
-    sediment_release(h);
+    h->sed = Handle::Sediment();
+    exner_release_unused(h);
     return SWE2D_OK;
 }
 
@@ -889,10 +852,10 @@ int swe2d_bedload_set(swe2d_handle *hh, const swe2d_bedload_params *par)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     Handle::Bedload &b = h->bed;
     const size_t S = h->stride;
-    if (int rc = exner_tables_build(h, "swe2d_bedload_set")) return rc;
-    if (int rc = gradient_table_build(h, "swe2d_bedload_set")) return rc;
+    if (int rc = exner_tables_build(h)) return rc;
+    if (int rc = gradient_table_build(h)) return rc;
     if (!b.planes) {
-        HIP_TRY(h, hipMalloc(&b.planes, 9*S*sizeof(double)));
+        HIP_TRY(h, b.planes.alloc(9*S));
         HIP_TRY(h, hipMemsetAsync(b.planes, 0, 9*S*sizeof(double), h->stream));
     }
     b.par = *par;
@@ -932,8 +895,8 @@ int swe2d_bedload_clear(swe2d_handle *hh)
     if (!h->bed.on) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    bedload_release(h);
-    if (!h->sed.on && !h->slide.on) sediment_release_tables(h);
+    h->bed = Handle::Bedload();
+    exner_release_unused(h);
     return SWE2D_OK;
 }
 
@@ -959,20 +922,19 @@ int swe2d_slide_set(swe2d_handle *hh, const swe2d_slide_params *par, const doubl
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     Handle::Slide &sl = h->slide;
     const size_t S = h->stride;
-    if (int rc = exner_tables_build(h, "swe2d_slide_set")) return rc;
-    if (int rc = gradient_table_build(h, "swe2d_slide_set")) return rc;
+    if (int rc = exner_tables_build(h)) return rc;
+    if (int rc = gradient_table_build(h)) return rc;
     if (!sl.planes) {
-        HIP_TRY(h, hipMalloc(&sl.planes, 5*S*sizeof(double)));
+        HIP_TRY(h, sl.planes.alloc(5*S));
         HIP_TRY(h, hipMemsetAsync(sl.planes, 0, 5*S*sizeof(double), h->stream));
     }
-    if (!sl.words) HIP_TRY(h, hipMalloc(&sl.words, 2*sizeof(unsigned long long)));
+    HIP_TRY(h, sl.words.ensure(2));
     HIP_TRY(h, hipMemsetAsync(sl.words, 0, 2*sizeof(unsigned long long), h->stream));
     if (region_per_cell) {
-        if (!sl.region) HIP_TRY(h, hipMalloc(&sl.region, (size_t)h->n_cells*sizeof(double)));
+        HIP_TRY(h, sl.region.ensure((size_t)h->n_cells));
         HIP_TRY(h, hipMemcpyAsync(sl.region, region_per_cell, (size_t)h->n_cells*sizeof(double), hipMemcpyHostToDevice, h->stream));
-    } else if (sl.region) {
-        HIP_TRY(h, hipFree(sl.region));
-        sl.region = nullptr;
+    } else {
+        sl.region.reset();
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     sl.par = *par;
@@ -1040,8 +1002,8 @@ int swe2d_slide_clear(swe2d_handle *hh)
     if (!h->slide.on) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    slide_release(h);
-    if (!h->sed.on && !h->bed.on) sediment_release_tables(h);
+    h->slide = Handle::Slide();
+    exner_release_unused(h);
     return SWE2D_OK;
 }
 
@@ -1060,7 +1022,7 @@ int swe2d_exner_skipped(swe2d_handle *hh, int64_t *n_skipped)
     if (!n_skipped) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     unsigned c = 0;
-    HIP_TRY(h, hipMemcpyAsync(&c, h->sed.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&c, h->exner.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *n_skipped = (int64_t)c;
     return SWE2D_OK;

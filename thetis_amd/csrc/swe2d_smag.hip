@@ -177,16 +177,11 @@ int smag_check(Handle *h, const char *who)
 void smag_release(Handle *h)
 {
     Handle::Smag &s = h->smag;
-    void *ptrs[] = {s.he, s.off, s.ent, s.planes, s.nu_clip, s.grad, s.grad_out};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     if (s.on) {
         // the caller's viscosity takes its place again
-        if (h->nu_v) (void)hipFree(h->nu_v);
-        h->nu_v = s.bg_v;
+        h->nu_v = std::move(s.bg_v);
         h->nu_const = s.bg_const;
         h->visc = s.visc_caller;
-    } else if (s.bg_v) {
-        (void)hipFree(s.bg_v);
     }
     s = Handle::Smag();
 }
@@ -232,8 +227,6 @@ int swe2d_impl::smag_update_launch(Handle *h)
     return SWE2D_OK;
 }
 
-void swe2d_impl::smag_free(Handle *h) { smag_release(h); }
-
 extern "C" {
 
 int swe2d_smag_set(swe2d_handle *hh, double c_s, const double *h_elem_vertex, double min_val, double max_const_or_negative,
@@ -268,21 +261,20 @@ int swe2d_smag_set(swe2d_handle *hh, double c_s, const double *h_elem_vertex, do
     const size_t S = h->stride;
     if (!s.on) {
         // the caller's viscosity becomes the background, in a buffer of its own: nu_v is rewritten at every step
-        double *total = nullptr;
-        HIP_TRY(h, hipMalloc(&total, (size_t)nv*sizeof(double)));
+        DevArray<double> total;
+        HIP_TRY(h, total.alloc(nv));
         s.visc_caller = h->visc;
-        s.bg_v = h->visc ? h->nu_v : nullptr;
+        if (h->visc) s.bg_v = std::move(h->nu_v);          // (the array of a viscosity that was switched off goes with the next line)
         s.bg_const = h->visc ? h->nu_const : 0.0;
-        if (!h->visc && h->nu_v) (void)hipFree(h->nu_v);
-        h->nu_v = total;
+        h->nu_v = std::move(total);
         h->visc = true;
         s.on = true;
     }
-    if (!s.he) HIP_TRY(h, hipMalloc(&s.he, (size_t)nv*sizeof(double)));
-    if (!s.off) HIP_TRY(h, hipMalloc(&s.off, (size_t)(nv + 1)*sizeof(int)));
-    if (!s.ent) HIP_TRY(h, hipMalloc(&s.ent, (size_t)3*n*sizeof(int)));
-    if (!s.planes) HIP_TRY(h, hipMalloc(&s.planes, 4*S*sizeof(double)));
-    if (!s.nu_clip) HIP_TRY(h, hipMalloc(&s.nu_clip, (size_t)nv*sizeof(double)));
+    HIP_TRY(h, s.he.ensure(nv));
+    HIP_TRY(h, s.off.ensure((size_t)(nv + 1)));
+    HIP_TRY(h, s.ent.ensure((size_t)3*n));
+    HIP_TRY(h, s.planes.ensure(4*S));
+    HIP_TRY(h, s.nu_clip.ensure(nv));
     HIP_TRY(h, hipMemcpyAsync(s.he, h_elem_vertex, (size_t)nv*sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(s.off, vertex_cell_ptr, (size_t)(nv + 1)*sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(s.ent, vertex_cell_idx, (size_t)3*n*sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -326,8 +318,8 @@ int swe2d_smag_read(swe2d_handle *hh, int which, double *out)
     switch (which) {
     case SWE2D_SMAG_GRADIENT:
         // the debug flag: the cell pass once more on the state that is there, with the 12 gradient planes written
-        if (!s.grad) HIP_TRY(h, hipMalloc(&s.grad, 12*S*sizeof(double)));
-        if (!s.grad_out) HIP_TRY(h, hipMalloc(&s.grad_out, 12*n*sizeof(double)));
+        HIP_TRY(h, s.grad.ensure(12*S));
+        HIP_TRY(h, s.grad_out.ensure(12*n));
         if (int rc = smag_cell_launch(h, true)) return rc;
         hipLaunchKernelGGL(swe_planes_to_nodal, dim3(grid_for(h->n_cells)), dim3(256), 0, h->stream, s.grad, s.grad_out, S, h->n_cells, 12);
         HIP_TRY(h, hipGetLastError());

@@ -96,12 +96,6 @@ int stats_check(Handle *h, int id, Handle::Stats **out)
     return SWE2D_OK;
 }
 
-void stats_release(Handle::Stats &s)
-{
-    if (s.acc) (void)hipFree(s.acc);
-    s = Handle::Stats();
-}
-
 int stats_fill(Handle *h, const Handle::Stats &s)
 {
     const size_t plane_set = (size_t)h->npc*h->stride, total = (size_t)(SWE_STATS_FIXED + 2*s.K)*plane_set;
@@ -112,12 +106,6 @@ int stats_fill(Handle *h, const Handle::Stats &s)
 }
 
 }  // namespace
-
-void swe2d_impl::stats_free_all(Handle *h)
-{
-    for (auto &s : h->stats) stats_release(s);
-    h->stats.clear();
-}
 
 int swe2d_stats_create(swe2d_handle *hh, int32_t n_constituents, int32_t *stats_id)
 {
@@ -131,17 +119,12 @@ int swe2d_stats_create(swe2d_handle *hh, int32_t n_constituents, int32_t *stats_
     Handle::Stats s;
     s.K = n_constituents;
     const size_t bytes = (size_t)(SWE_STATS_FIXED + 2*s.K)*h->npc*h->stride*sizeof(double);
-    const hipError_t e = hipMalloc(&s.acc, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        s.acc = nullptr;
-        return fail(h, SWE2D_ERR_HIP, "swe2d_stats_create: " + std::to_string(bytes) + " bytes of accumulator planes: " + hipGetErrorString(e));
-    }
-    if (int rc = stats_fill(h, s)) { stats_release(s); return rc; }
+    HIP_TRY(h, s.acc.alloc(bytes/sizeof(double)));
+    if (int rc = stats_fill(h, s)) return rc;
     s.live = true;
     int id = 0;
     while (id < (int)h->stats.size() && h->stats[id].live) id++;
-    if (id == (int)h->stats.size()) h->stats.push_back(s); else h->stats[id] = s;
+    if (id == (int)h->stats.size()) h->stats.push_back(std::move(s)); else h->stats[id] = std::move(s);
     *stats_id = id;
     return SWE2D_OK;
 }
@@ -218,6 +201,6 @@ int swe2d_stats_destroy(swe2d_handle *hh, int32_t id)
     if (int rc = stats_check(h, id, &s)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                           // samples may still be in flight
-    stats_release(*s);
+    *s = Handle::Stats();
     return SWE2D_OK;
 }

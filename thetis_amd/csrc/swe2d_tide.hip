@@ -51,20 +51,6 @@ __global__ void __launch_bounds__(256) swe_tide_gather_kernel(const double *plan
     swe_st(swe_rsrc(out), (unsigned)p*8u, 0u, swe_ld(swe_rsrc(planes), ((unsigned)(2*f + (p & 1))*stride + (unsigned)c)*8u, 0u));
 }
 
-namespace {
-
-void tide_release(Handle *h)
-{
-    Handle::Tide &td = h->tide;
-    if (td.tab) (void)hipFree(td.tab);
-    if (td.list) (void)hipFree(td.list);
-    if (td.out) (void)hipFree(td.out);
-    td = Handle::Tide();
-}
-
-}  // namespace
-
-void swe2d_impl::tide_free(Handle *h) { tide_release(h); }
 
 int swe2d_impl::tide_launch(Handle *h, double t)
 {
@@ -120,16 +106,16 @@ int swe2d_tide_set(swe2d_handle *hh, int32_t n_facets, const int32_t *cells, con
     for (size_t k = 0; k < K; k++) if (!std::isfinite(omega[k])) return fail(h, SWE2D_ERR_INVALID_ARGUMENT, "swe2d_tide_set: the table must be finite");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                          // launches that read the old table are done
-    tide_release(h);                                                      // (the clock is the handle's: a new table keeps it)
+    h->tide = Handle::Tide();                                                      // (the clock is the handle's: a new table keeps it)
     Handle::Tide &td = h->tide;
     if (!h->bc_field[0]) {                                                // as swe2d_set_bc_facets
         const size_t bytes = (size_t)2*h->npc*h->stride*sizeof(double);
-        HIP_TRY(h, hipMalloc(&h->bc_field[0], bytes));
+        HIP_TRY(h, h->bc_field[0].alloc(bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(h->bc_field[0], 0, bytes, h->stream));
     }
-    HIP_TRY(h, hipMalloc(&td.tab, (1 + 2*K)*nn*sizeof(double)));
-    HIP_TRY(h, hipMalloc(&td.list, nn*sizeof(int)));
-    HIP_TRY(h, hipMalloc(&td.out, nn*sizeof(double)));
+    HIP_TRY(h, td.tab.alloc((1 + 2*K)*nn));
+    HIP_TRY(h, td.list.alloc(nn));
+    HIP_TRY(h, td.out.alloc(nn));
     HIP_TRY(h, hipMemcpyAsync(td.tab, mean, nn*sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(td.tab + nn, amp, K*nn*sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(td.tab + nn*(1 + K), phase, K*nn*sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -150,7 +136,7 @@ int swe2d_tide_clear(swe2d_handle *hh)
     if (h->tide.n == 0) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    tide_release(h);
+    h->tide = Handle::Tide();
     return SWE2D_OK;
 }
 

@@ -96,17 +96,6 @@ bool swe2d_impl::farm_capturing(Handle *h)
     return yes;
 }
 
-void swe2d_impl::farm_release(Handle::Farm &f)
-{
-    if (f.density) (void)hipFree(f.density);
-    if (f.cells) (void)hipFree(f.cells);
-    if (f.dtab) (void)hipFree(f.dtab);
-    if (f.txy) (void)hipFree(f.txy);
-    if (f.csr) (void)hipFree(f.csr);
-    if (f.tpow) (void)hipFree(f.tpow);
-    f = Handle::Farm();
-}
-
 // the device's copy of the farms' constants, rebuilt after every change (the stream is idle: the callers synchronise first)
 // A discrete slot has its constants in the table but is not live in it: the stage kernels and swe_turbine_power_kernel pass it by,
 // the passes of swe2d_dfarm.hip read f[m].
@@ -140,7 +129,7 @@ int swe2d_impl::farm_upload_table(Handle *h)
         if (!f.discrete) blocks += (f.n_list + SWE_BLOCK - 1)/SWE_BLOCK;
     }
     h->farm_blocks = blocks;
-    if (!h->farm_table) HIP_TRY(h, hipMalloc(&h->farm_table, sizeof(SweFarmTable)));
+    HIP_TRY(h, h->farm_table.ensure(1));
     HIP_TRY(h, hipMemcpy(h->farm_table, &t, sizeof(t), hipMemcpyHostToDevice));
     return SWE2D_OK;
 }
@@ -148,8 +137,8 @@ int swe2d_impl::farm_upload_table(Handle *h)
 int swe2d_impl::farm_rows_alloc(Handle *h, int capacity)
 {
     if (h->farm_rows && h->farm_rows_cap == capacity) return SWE2D_OK;
-    if (h->farm_rows) { HIP_TRY(h, hipStreamSynchronize(h->stream)); HIP_TRY(h, hipFree(h->farm_rows)); h->farm_rows = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->farm_rows, ((size_t)capacity + 1)*SWE_FARM_ROW*sizeof(unsigned long long)));
+    if (h->farm_rows) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->farm_rows.alloc(((size_t)capacity + 1)*SWE_FARM_ROW));
     h->farm_rows_cap = capacity;
     h->farm_rows_n = 0;
     return SWE2D_OK;
@@ -175,14 +164,6 @@ int launch_power(Handle *h, unsigned long long *row)
 }
 
 }  // namespace
-
-void swe2d_impl::farm_free_all(Handle *h)
-{
-    for (auto &f : h->farms) farm_release(f);
-    h->n_farms = h->n_cfarms = 0;
-    if (h->farm_table) { (void)hipFree(h->farm_table); h->farm_table = nullptr; }
-    if (h->farm_rows) { (void)hipFree(h->farm_rows); h->farm_rows = nullptr; }
-}
 
 extern "C" {
 
@@ -213,16 +194,16 @@ int swe2d_turbine_farm_set(swe2d_handle *hh, int32_t farm, const swe2d_turbine_p
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                          // launches that read the old table / density are done
     Handle::Farm &f = h->farms[farm];
-    if (f.discrete) farm_release(f);                                      // the slot changes its kind
+    if (f.discrete) f = Handle::Farm();                                   // the slot changes its kind
     const size_t plane_bytes = (size_t)h->npc*h->stride*sizeof(double);
     if (!f.density) {
-        HIP_TRY(h, hipMalloc(&f.density, plane_bytes));
+        HIP_TRY(h, f.density.alloc(plane_bytes/sizeof(double)));
         HIP_TRY(h, hipMemsetAsync(f.density, 0, plane_bytes, h->stream));
     }
-    if (f.cells) { HIP_TRY(h, hipFree(f.cells)); f.cells = nullptr; }
+    f.cells.reset();
     f.n_list = (int)list.size();
     if (f.n_list) {
-        HIP_TRY(h, hipMalloc(&f.cells, list.size()*sizeof(int)));
+        HIP_TRY(h, f.cells.alloc(list.size()));
         HIP_TRY(h, hipMemcpyAsync(f.cells, list.data(), list.size()*sizeof(int), hipMemcpyHostToDevice, h->stream));
     }
     HIP_TRY(h, hipMemcpyAsync(h->stage_uv, density_nodal, n*sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -245,7 +226,7 @@ int swe2d_turbine_farm_clear(swe2d_handle *hh, int32_t farm)
     if (!h->farms[farm].live) return SWE2D_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    farm_release(h->farms[farm]);
+    h->farms[farm] = Handle::Farm();
     return farm_upload_table(h);
 }
 
